@@ -10,11 +10,16 @@ per-lane seeds seed0 + global lane for auto-reset.  Weak scaling: every GPU owns
 [rank*B, (rank+1)*B)), no collective on the data path.
 
     python bench.py [--gpus N --steps K --warmup W --boards B --rng pcg64|philox --obs log2|onehot|raw|none]
+                    [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...
 
-Rank 0 prints ONE JSON line.  Extras: `roofline` of the step kernel (SURVEY.md section 8(d)'s algorithmic bytes per
-board-step / HIP-event kernel time vs 8 TB/s; the build's layout bytes beside them; `traffic` = HBM bytes per launch
-from rocprofv3 FETCH_SIZE/WRITE_SIZE passes when rocprofv3 is present), `cpu_baseline` (the reference's CPU step
+Rank 0 prints ONE JSON line.  A plain run does only what the headline needs: it builds the inputs, warms the chip up,
+runs W untimed and K timed launches and prints the line (`value`, `ms_per_step` = wall milliseconds per timed launch,
+and the step kernel's `roofline` from HIP events around the same K launches, `traffic` null).  --dump-outputs DIR
+then writes what the last timed launch returned (see dump_outputs).  Everything else runs only with --full, each leg
+with its own --no-* switch.  Extras of --full: the `roofline` (SURVEY.md section 8(d)'s algorithmic bytes per
+board-step / HIP-event kernel time vs 8 TB/s; the build's layout bytes beside them) gains `traffic` = HBM bytes per
+launch from rocprofv3 FETCH_SIZE/WRITE_SIZE passes when rocprofv3 is present, `cpu_baseline` (the reference's CPU step
 loop restated in Python -- oracle/pyref.py, pinned to the reference -- one process per host core, a bounded sample;
 the C port beside it), `configs4_onehot_philox` (configs[4]'s per-GPU shard, every rank: the same step leg in Philox
 mode writing one-hot obs + int8 mask, 1,122 B / board-step, with its own roofline and PMC traffic),
@@ -77,6 +82,11 @@ def parse():
     ap.add_argument("--boards", type=int, default=1 << 20, help="boards per GPU")
     ap.add_argument("--rng", default="pcg64", choices=["pcg64", "philox"])
     ap.add_argument("--obs", default="log2", choices=["log2", "onehot", "raw", "none"])
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the extra legs: PMC traffic, CPU baseline, configs[4] leg, training iterations, "
+                         "policy rollouts (each has its own --no-* switch)")
     ap.add_argument("--cpu-baseline-seconds", type=float, default=10.0)
     ap.add_argument("--train-episodes", type=int, default=1 << 19,
                     help="episodes per GPU of the data-parallel training-iteration leg (configs[3]'s shard)")
@@ -511,6 +521,39 @@ def onehot_philox_leg(torch, args, B, rank, world, device, actions, K, W, traffi
     return out
 
 
+# ---------------------------------------------------------------------------------------------- outputs
+DUMP_BUDGET_BYTES = 48 << 20   # all arrays together; well inside 64 MB
+
+
+def dump_outputs(torch, env, out_dir: str, with_obs: bool) -> dict:
+    """What the last timed step_into returned to its caller, as out_dir/<name>.npy: `reward` float32 [S], `flags`
+    float32 [S] (the G2048_F_* byte), `action_mask` float32 [S,4], `obs` float32 [S,obs_width] (unless --obs none)
+    and the stepped `board` as float32 [S,16] tile exponents, for the S lanes listed in `lanes` (float64 [S]).  S is
+    every lane when that fits the byte budget, else a fixed sample: the first S of numpy's default_rng(0x2048)
+    permutation of the lanes, sorted -- a function of --boards and --obs only, so two runs with the same arguments
+    write the same lanes of the same inputs."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    n = env.n
+    per_lane = 4 * (1 + 1 + 4 + 16 + (env.obs_width if with_obs else 0)) + 8
+    S = min(n, DUMP_BUDGET_BYTES // per_lane)
+    lanes = np.arange(n) if S == n else np.sort(np.random.default_rng(0x2048).permutation(n)[:S])
+    it = torch.from_numpy(lanes).to(env.device)
+    arrays = {"lanes": lanes.astype(np.float64),
+              "reward": env.reward[it].cpu().numpy().astype(np.float32),
+              "flags": env.flags[it].cpu().numpy().astype(np.float32),
+              "action_mask": env.action_mask[it].cpu().numpy().astype(np.float32),
+              "board": ((env.board[it].unsqueeze(1) >> torch.arange(0, 64, 4, device=env.device)) & 15)
+                       .cpu().numpy().astype(np.float32)}
+    if with_obs:
+        arrays["obs"] = env.obs[it].cpu().numpy().astype(np.float32)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {"dir": out_dir, "lanes": int(S), "of": int(n), "bytes": int(sum(a.nbytes for a in arrays.values())),
+            "arrays": {k: list(a.shape) for k, a in arrays.items()}}
+
+
 # ---------------------------------------------------------------------------------------------- main
 def main():
     args = parse()
@@ -523,13 +566,14 @@ def main():
     # torchrun the other ranks meanwhile wait in init_process_group (well inside its timeout), so the CPU loop is
     # timed on the same box's host cores in the same run and the roofline carries PMC traffic at N > 1 too.
     traffic = traffic4 = None
-    run_c4 = not args.pmc_child and not args.no_configs4
-    if rank == 0 and not args.pmc_child and args.traffic == "auto":
+    full = args.full and not args.pmc_child
+    run_c4 = full and not args.no_configs4
+    if rank == 0 and full and args.traffic == "auto":
         traffic = pmc_traffic(args)
         if run_c4:
             traffic4 = pmc_traffic(args, rng="philox", obs="onehot")
     cpu = None
-    if rank == 0 and not args.pmc_child and not args.no_cpu_baseline:
+    if rank == 0 and full and not args.no_cpu_baseline:
         cpu = cpu_baseline(args, args.cpu_baseline_seconds)
 
     import torch
@@ -560,13 +604,13 @@ def main():
     # timed on a chip at its working clock: on a cold chip the first ~20 launches of the step kernel run 10-30 %
     # slower (profiles/round3/step_cold_trace.log), which a 20-step run would otherwise fold into the headline.
     train = None
-    if not args.pmc_child and not args.no_train and args.train_episodes > 0:
+    if full and not args.no_train and args.train_episodes > 0:
         try:
             train = train_iteration_dp(torch, device, args.train_episodes, rank, world)
         except Exception as e:  # noqa: BLE001 -- an extra, never the headline
             train = {"error": repr(e)}
     policy = None
-    if not args.pmc_child and rank == 0 and world == 1 and not args.no_policy:
+    if full and rank == 0 and world == 1 and not args.no_policy:
         try:
             policy = policy_rollout_rate(torch, B, device)
             policy["gemm_path"] = policy_rollout_rate(torch, B, device, fused=False)
@@ -642,6 +686,7 @@ def main():
         dist.destroy_process_group()
     if rank != 0:
         return
+    dumped = dump_outputs(torch, env, args.dump_outputs, args.obs != "none") if args.dump_outputs else None
     rb, wb = bytes_per_step(args.rng, args.obs)
     sb = survey_bytes_per_step(args.rng, args.obs)
     alg_bytes = sb * B
@@ -673,6 +718,8 @@ def main():
     }
     if traffic:
         line["roofline"]["traffic_detail"] = traffic
+    if dumped is not None:
+        line["dumped_outputs"] = dumped
     if configs4 is not None:
         line["configs4_onehot_philox"] = configs4
     if train is not None:

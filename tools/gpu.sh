@@ -7,9 +7,9 @@
 # steps:
 #   tests[:ARGS]        pytest -m gpu over ARGS (shell-parsed after the colon; default: the whole suite)
 #   smoke               __graft_entry__.smoke()
-#   bench               the driver's bench command (bench.py --gpus 1 --steps 20 --warmup 5)
+#   bench               the whole bench line, every leg (bench.py --full --gpus 1 --steps 20 --warmup 5)
 #   prof_step           rocprofv3 kernel stats of 200 step-kernel launches (bench.py step leg only)
-#   trace_bench         the driver's bench command under a rocprofv3 kernel trace; tools/trace_window.py reads the
+#   trace_bench         the same bench command under a rocprofv3 kernel trace; tools/trace_window.py reads the
 #                       timed launches back (headline + configs[4] legs) beside the line's kernel_ms
 #   rehearse8           bench.py under torchrun with 8 ranks sharing the one GPU (gloo): the N = 8 flow end to end
 #   prof_c4             rocprofv3 kernel stats of 200 launches of configs[4]'s Philox + one-hot step leg
@@ -72,7 +72,7 @@ for step in "$@"; do
         tail -1 "$O/smoke.log"
         ;;
     bench)
-        timeout -k 10 400 python3 bench.py --gpus 1 --steps 20 --warmup 5 > "$O/bench_driver_cmd.log" 2>&1 ||
+        timeout -k 10 400 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > "$O/bench_driver_cmd.log" 2>&1 ||
             { tail -20 "$O/bench_driver_cmd.log"; exit 1; }
         grep '^{' "$O/bench_driver_cmd.log" | cut -c1-400
         ;;
@@ -80,7 +80,7 @@ for step in "$@"; do
         # the driver's bench command itself under a rocprofv3 kernel trace: its timed launches read back
         # (tools/trace_window.py) beside the line's HIP-event kernel_ms; then the per-kernel stats of the same run
         timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/trace_bench" -o tb -- \
-            python3 bench.py --gpus 1 --steps 20 --warmup 5 > "$O/trace_bench.log" 2>&1 ||
+            python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > "$O/trace_bench.log" 2>&1 ||
             { tail -20 "$O/trace_bench.log"; exit 1; }
         grep '^{' "$O/trace_bench.log" | cut -c1-300
         python3 tools/trace_window.py "$O/trace_bench" "$O/trace_bench.log" --keep "$O/trace_bench_step_rows.csv" \
@@ -100,7 +100,7 @@ for step in "$@"; do
         # bench.py's N = 8 flow on ONE GPU (8 ranks share it: the gloo fallback) -- rank 0's PMC children and CPU
         # baseline before init_process_group, every leg's barriers and max-over-ranks reduce; value is not scaling
         HSA_ENABLE_IPC_MODE_LEGACY=0 timeout -k 10 900 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 8 \
-            --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 8 --steps 20 --warmup 5 --boards 65536 \
+            --master-addr 127.0.0.1 --master-port 29533 bench.py --full --gpus 8 --steps 20 --warmup 5 --boards 65536 \
             --train-episodes 4096 > "$O/rehearse8.log" 2>&1 || { tail -30 "$O/rehearse8.log"; exit 1; }
         grep '^{' "$O/rehearse8.log" | cut -c1-400
         ;;

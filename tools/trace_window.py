@@ -1,6 +1,6 @@
 """TOOL: the bench line's timed launches read back from a rocprofv3 kernel trace of the same command.
 
-    rocprofv3 --kernel-trace --output-format csv -d D -o run -- python3 bench.py --gpus 1 --steps 20 --warmup 5 > b.log
+    rocprofv3 --kernel-trace --output-format csv -d D -o run -- python3 bench.py --full --steps 20 --warmup 5 > b.log
     python tools/trace_window.py D b.log [--keep OUT.csv]
     python tools/trace_window.py OUT.csv b.log          (the same figures from a kept file)
 
