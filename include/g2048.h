@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define G2048_ABI_VERSION 16
+#define G2048_ABI_VERSION 17
 
 /* status codes */
 #define G2048_OK 0
@@ -71,7 +71,8 @@ extern "C" {
 #define G2048_LS_HAS_U32 0x04000000u
 #define G2048_MAX_STEPS_LIMIT 0x000FFFFF
 
-/* Game2048EnvConfig (src/env.py:19-40).  size is fixed at 4. */
+/* Game2048EnvConfig (src/env.py:19-40) without its size field: the board size is an argument of the entry points.
+ * The entry points above the "sized" section are the 4 x 4 product path; g2048_sized_* take any size in 2..8. */
 typedef struct g2048_env_cfg {
     int32_t obs_mode;              /* G2048_OBS_* */
     int32_t reward_mode;           /* 0 "sum", 1 "log2" */
@@ -431,5 +432,8 @@ int g2048_onehot_dw1(const uint64_t* boards, const float* d1, int h1, int64_t m,
 #ifdef __cplusplus
 }
 #endif
+
+/* board sizes 2..8: the g2048_sized_* entry points (ABI 17), part of this interface */
+#include "g2048_sized.h"
 
 #endif /* G2048_H */

@@ -1,0 +1,70 @@
+/*
+ * g2048_sized.h -- the part of the C ABI of libg2048.so (include/g2048.h, which includes this file) that serves
+ * board sizes other than 4.  Include g2048.h, not this file: it uses the types and constants declared there.
+ */
+#ifndef G2048_SIZED_H
+#define G2048_SIZED_H
+
+#ifndef G2048_H
+#error "include g2048.h"
+#endif
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* ---- board sizes 2..8 (g2048_sized.hip; ABI 17) -------------------------------------------------------------------
+ * Game2048 / Game2048Env for Game2048EnvConfig.size = N, 2 <= N <= 8 (src/game2048.py never assumes 4).  Board
+ * encoding: cell k = r*N + c lives in nibble (k & 15) of word (k >> 4), W = g2048_sized_words(N) = ceil(N*N / 16)
+ * uint64 words per board (1 for N <= 4, 2 for 5, 3 for 6, 4 for 7 and 8); unused high nibbles are 0; saturation at
+ * 2**15 and G2048_F_OVERFLOW as above.  Board buffers are plane-major: word w of lane i at buf[w * plane_stride + i],
+ * plane_stride >= n given per buffer (so prev_board can be row t of a [W, cap, n] trajectory tensor with
+ * plane_stride = cap * n).  Lines move in plain ALU (no row table; g2048_init is not needed).  The lane state word,
+ * flag bits, seeds, PCG64 arrays, Philox counter / key scheme and every other argument are those of the 4 x 4
+ * counterparts.  obs buffers are [n * N*N] (raw / log2) or [n * N*N*17] (one-hot, channel e of cell r*N+c at
+ * (r*N+c)*17 + e) and must be 16-byte aligned.  Every entry point accepts N = 4 too (W = 1, same results as the 4 x 4
+ * entry points; the product path does not use them).  A size outside 2..8, a plane_stride below the lanes it must
+ * hold or n > 2^30 return G2048_EINVAL before any launch. */
+int g2048_sized_words(int size);   /* W, or -1 for an unsupported size */
+
+/* g2048_step_out for sized boards: the same fields, except */
+typedef struct g2048_sized_step_out {
+    float* reward;
+    uint8_t* flags;
+    int8_t* mask;
+    float* obs;
+    uint8_t* merged;       /* [n][N*(N/2)] the exponent log2(v) of each merged tile of this step in the reference's
+                              list order (board rotated clockwise 3 - action times, rows top to bottom, each left to
+                              right: src/game2048.py:120-165), 0-terminated when shorter than N*(N/2) */
+    uint64_t* prev_board;  /* planes of the board before the step, word w of lane i at [w * prev_stride + i] */
+    double* reward64;
+    uint32_t* score_add;
+    uint8_t* mask_bits;
+    int64_t prev_stride;   /* plane stride of prev_board (>= n; ignored when prev_board is NULL) */
+} g2048_sized_step_out;
+
+/* g2048_reset for size N: lanes->board holds W planes of plane_stride lanes. */
+int g2048_sized_reset(int size, const g2048_lanes* lanes, int64_t plane_stride, const uint64_t* seeds,
+                      const uint8_t* reset_mask, const g2048_env_cfg* cfg, int rng_mode, uint64_t philox_key,
+                      int8_t* mask_out, float* obs_out, int64_t n, void* stream);
+/* g2048_step for size N (one kernel: move, spawn, done, fp64 reward, flags, truncation, max_tile_seen, auto-reset). */
+int g2048_sized_step(int size, const g2048_lanes* lanes, int64_t plane_stride, const uint8_t* actions,
+                     const g2048_env_cfg* cfg, const g2048_sized_step_out* out, int rng_mode, uint64_t philox_key,
+                     int auto_reset, uint64_t reset_stride, int64_t n, void* stream);
+/* g2048_obs for size N. */
+int g2048_sized_obs(int size, const uint64_t* boards, int64_t plane_stride, int obs_mode, float obs_log2_scale,
+                    float* obs, int8_t* mask, int64_t n, void* stream);
+/* g2048_move for size N: out_board planes of out_stride lanes; merged [n][N*(N/2)] as in g2048_sized_step_out. */
+int g2048_sized_move(int size, const uint64_t* boards, int64_t plane_stride, const uint8_t* actions,
+                     uint64_t* out_board, int64_t out_stride, uint8_t* merged, uint8_t* flags, int64_t n,
+                     void* stream);
+/* g2048_symmetries for size N: word w of symmetry k of lane i at out_boards[w * out_stride + k*n + i]
+ * (out_stride >= 8n); out_actions [8n] symmetry-major (NULL ok). */
+int g2048_sized_symmetries(int size, const uint64_t* boards, int64_t plane_stride, const uint8_t* actions,
+                           uint64_t* out_boards, int64_t out_stride, uint8_t* out_actions, int64_t n, void* stream);
+
+#ifdef __cplusplus
+}
+#endif
+
+#endif /* G2048_SIZED_H */

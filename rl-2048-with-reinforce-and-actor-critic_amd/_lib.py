@@ -19,9 +19,9 @@ SHIPPED_LIB = os.path.join(PKG_DIR, "libg2048.so")
 LIB_PATH = SHIPPED_LIB
 SRC = os.path.join(PKG_DIR, "csrc", "g2048.hip")
 SOURCES = [SRC, os.path.join(PKG_DIR, "csrc", "g2048_policy.hip"), os.path.join(PKG_DIR, "csrc", "g2048_dw2.hip"),
-           os.path.join(PKG_DIR, "csrc", "g2048_deep.hip")]
+           os.path.join(PKG_DIR, "csrc", "g2048_deep.hip"), os.path.join(PKG_DIR, "csrc", "g2048_sized.hip")]
 INCLUDE = os.path.join(REPO_ROOT, "include")
-ABI_VERSION = 16
+ABI_VERSION = 17
 DEEP_MAX_HIDDEN = 4
 
 # include/g2048.h constants
@@ -66,7 +66,7 @@ def _object_for(src: str, flags: list[str]) -> str:
     h = hashlib.sha256(" ".join(flags).encode())
     h.update(_compiler_id().encode())
     hdrs = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".inc")))
-    for f in [src] + hdrs + [os.path.join(INCLUDE, "g2048.h")]:
+    for f in [src] + hdrs + [os.path.join(INCLUDE, "g2048.h"), os.path.join(INCLUDE, "g2048_sized.h")]:
         with open(f, "rb") as fh:
             h.update(fh.read())
     return os.path.join(BUILD_DIR, f"{os.path.splitext(os.path.basename(src))[0]}-{h.hexdigest()[:16]}.o")
@@ -125,6 +125,13 @@ class Lanes(ctypes.Structure):
 class StepOut(ctypes.Structure):
     _fields_ = [(name, ctypes.c_void_p) for name in ("reward", "flags", "mask", "obs", "merged", "prev_board",
                                                          "reward64", "score_add", "mask_bits")]
+
+
+class SizedStepOut(ctypes.Structure):
+    """g2048_sized_step_out: StepOut with a byte merged list and the plane stride of prev_board."""
+    _fields_ = [(name, ctypes.c_void_p) for name in ("reward", "flags", "mask", "obs", "merged", "prev_board",
+                                                         "reward64", "score_add", "mask_bits")] + \
+               [("prev_stride", ctypes.c_int64)]
 
 
 class Traj(ctypes.Structure):
@@ -205,6 +212,15 @@ def _declare(L):
     L.g2048_onehot_dw1_slab.argtypes = [i32]
     L.g2048_onehot_dw1_slab.restype = i64
     L.g2048_onehot_dw1.argtypes = [vp, vp, i32, i64, i64, i64, vp, i64, vp]
+    L.g2048_sized_words.argtypes = [i32]
+    L.g2048_sized_reset.argtypes = [i32, P(Lanes), i64, vp, vp, P(EnvCfg), i32, u64, vp, vp, i64, vp]
+    L.g2048_sized_step.argtypes = [i32, P(Lanes), i64, vp, P(EnvCfg), P(SizedStepOut), i32, u64, i32, u64, i64, vp]
+    L.g2048_sized_obs.argtypes = [i32, vp, i64, i32, f, vp, vp, i64, vp]
+    L.g2048_sized_move.argtypes = [i32, vp, i64, vp, vp, i64, vp, vp, i64, vp]
+    L.g2048_sized_symmetries.argtypes = [i32, vp, i64, vp, vp, i64, vp, i64, vp]
+    for name in ("g2048_sized_words", "g2048_sized_reset", "g2048_sized_step", "g2048_sized_obs", "g2048_sized_move",
+                 "g2048_sized_symmetries"):
+        getattr(L, name).restype = ctypes.c_int
     for name in ("g2048_init", "g2048_seed_pcg64", "g2048_reset", "g2048_step", "g2048_obs", "g2048_move",
                  "g2048_sample", "g2048_returns", "g2048_symmetries", "g2048_policy_pack", "g2048_policy",
                  "g2048_rollout", "g2048_grad_pack", "g2048_actor_grad_waves", "g2048_actor_grad", "g2048_critic_grad",
@@ -224,6 +240,9 @@ EXPORTED_SYMBOLS = ("g2048_abi_version", "g2048_last_error", "g2048_init", "g204
                     "g2048_deep_grad_parts", "g2048_deep_grad_passes",
                     "g2048_deep_grad_pack", "g2048_deep_grad", "g2048_onehot_layer1", "g2048_onehot_dw1_slab",
                     "g2048_onehot_dw1")
+# include/g2048_sized.h (included by g2048.h): board sizes 2..8
+SIZED_SYMBOLS = ("g2048_sized_words", "g2048_sized_reset", "g2048_sized_step", "g2048_sized_obs", "g2048_sized_move",
+                 "g2048_sized_symmetries")
 
 
 def lib():

@@ -33,7 +33,7 @@ import numpy as np
 import torch
 from . import _lib as L
 from . import dp
-from .config import Game2048EnvConfig, obs_width
+from .config import check_size, Game2048EnvConfig, obs_width
 from .mlp import (MLPConfig, encode_observation, forward_logits, init_model_params, load_model_params, mlp_backward_,
                   mlp_forward_kept,
                   logits_to_probs, save_model_params)
@@ -68,14 +68,14 @@ class ReinforceAgentConfig:
 class TrajectoryBatch:
     """Device trajectory buffer of one batch of episodes, time-major: row t, column = episode (lane).
     boards[t, i] is the board BEFORE action actions[t, i]; rewards[t, i] its reward; valid iff t < lengths[i]."""
-    boards: torch.Tensor       # [T, n] int64 bitboards
+    boards: torch.Tensor       # [T, n] int64 bitboards (size 4); [W, T, n] board planes for any other size
     actions: torch.Tensor      # [T, n] uint8
     rewards: torch.Tensor      # [T, n] float64 (the Python float Game2048Env.step returns)
     flags: torch.Tensor        # [T, n] uint8 (G2048_F_*)
     lengths: torch.Tensor      # [n] int32
     total_reward: torch.Tensor  # [n] float64
     max_tile: torch.Tensor     # [n] int64 (Game2048Env.max_tile_seen at the end of the episode)
-    final_boards: torch.Tensor  # [n] int64
+    final_boards: torch.Tensor  # [n] int64 (size 4); [W, n] for any other size
     probs: torch.Tensor | None = None  # [T, n, 4] policy probabilities used for each draw (record_probs=True)
     # data parallel: the episode count of every rank's shard of the global batch (dp.shard_sizes), set by whoever
     # sharded it; lets the rank-weight all-gather run without a host synchronisation
@@ -87,7 +87,7 @@ class TrajectoryBatch:
 
     @property
     def T(self) -> int:
-        return int(self.boards.shape[0])
+        return int(self.actions.shape[0])
 
 
 def _seed_seq(seeds):
@@ -196,8 +196,14 @@ class _Steps:
         self.N = int(self.vidx.numel())
 
     # ---------------------------------------------------------------- features of flat time-major indices
+    def _gather(self, flat: torch.Tensor) -> torch.Tensor:
+        """The boards at flat time-major indices: [m] bitboards, or [W, m] planes for sizes other than 4."""
+        if self.agent._sized:
+            return self.boards.reshape(self.boards.shape[0], -1)[:, flat].contiguous()
+        return self.boards.reshape(-1)[flat].contiguous()
+
     def _board_obs(self, flat: torch.Tensor, k: int):
-        b = self.boards.reshape(-1)[flat].contiguous()
+        b = self._gather(flat)
         if k:
             b = self.agent._symmetry_boards(b, k)
         return self.agent._obs_from_boards(b)
@@ -222,7 +228,7 @@ class _Steps:
         flat = self.vidx[sel]
         if nxt:
             flat = torch.where(self.has_next[sel], flat + self.n, flat)
-        b = self.boards.reshape(-1)[flat].contiguous()
+        b = self._gather(flat)
         return self.agent._symmetry_boards(b, k) if k else b
 
     def actions_k(self, sel: torch.Tensor, k: int) -> torch.Tensor:
@@ -254,7 +260,11 @@ class ReinforceAgent:
             self._logger.addHandler(logging.NullHandler())
         if self.env is not None:
             self.env.reset(seed=0)       # the reference probes input_dim this way (src/reinforce_agent.py:70)
-        self.input_dim = obs_width(self.env_config.obs_mode)
+        self.size = check_size(self.env_config.size)
+        # sizes other than 4 run the general path only (hipBLASLt forward + g2048_sample + the sized env step, torch
+        # backprop): the fused policy / rollout / gradient kernels read 4 x 4 bitboards and are never offered one
+        self._sized = self.size != 4
+        self.input_dim = obs_width(self.env_config.obs_mode, self.size)
         self.n_actions = 4
         if initial_params_path is None:
             self.params = init_model_params(self.input_dim, self.mlp_config.hidden_sizes, self.n_actions, self.rng,
@@ -393,23 +403,37 @@ class ReinforceAgent:
         return L.stream_handle(self.device)
 
     def _obs_from_boards(self, boards: torch.Tensor):
-        m = boards.numel()
+        m = boards.shape[-1] if self._sized else boards.numel()
         x = torch.empty(m, self.input_dim, dtype=torch.float32, device=self.device)
         mk = torch.empty(m, 4, dtype=torch.int8, device=self.device)
+        if self._sized:      # boards: [W, m] planes
+            if m:
+                L.check(self._lib.g2048_sized_obs(self.size, L.ptr(boards), m, _OBS_CODE[self.env_config.obs_mode],
+                                                  float(self.env_config.obs_log2_scale), L.ptr(x), L.ptr(mk), m,
+                                                  self._stream))
+            return x, mk
         L.check(self._lib.g2048_obs(L.ptr(boards), _OBS_CODE[self.env_config.obs_mode],
                                     float(self.env_config.obs_log2_scale), L.ptr(x), L.ptr(mk), m, self._stream))
         return x, mk
 
     def _symmetry_boards(self, boards: torch.Tensor, k: int) -> torch.Tensor:
+        if self._sized:      # [W, m] planes -> symmetry k of each, [W, m]
+            W, m = boards.shape
+            out = torch.empty(W, 8 * m, dtype=torch.int64, device=self.device)
+            if m:
+                L.check(self._lib.g2048_sized_symmetries(self.size, L.ptr(boards), m, None, L.ptr(out), 8 * m, None,
+                                                         m, self._stream))
+            return out[:, k * m:(k + 1) * m].contiguous()
         m = boards.numel()
         out = torch.empty(8 * m, dtype=torch.int64, device=self.device)
         L.check(self._lib.g2048_symmetries(L.ptr(boards), None, L.ptr(out), None, m, self._stream))
         return out[k * m:(k + 1) * m]
 
     def _symmetry_features(self, x: torch.Tensor, m: torch.Tensor | None, k: int):
-        """get_symmetries (src/env.py:317-398) on host-provided features: board [.,4,4(,17)] and mask."""
-        onehot = x.shape[1] == 272
-        b = x.view(-1, 4, 4, 17) if onehot else x.view(-1, 4, 4)
+        """get_symmetries (src/env.py:317-398) on host-provided features: board [.,N,N(,17)] and mask."""
+        N = self.size
+        onehot = x.shape[1] == N * N * 17
+        b = x.view(-1, N, N, 17) if onehot else x.view(-1, N, N)
         if k >= 4:
             b = torch.flip(b, dims=[2])
             if m is not None:
@@ -446,7 +470,7 @@ class ReinforceAgent:
         return self._net_spec(self.critic_params, 1)
 
     def _net_spec(self, params=None, out_dim: int = 4):
-        if self.env_config.obs_mode not in ("log2", "raw"):
+        if self._sized or self.env_config.obs_mode not in ("log2", "raw"):
             return None
         params = self.params if params is None else params
         Ws, bs = params["W"], params["b"]
@@ -465,6 +489,8 @@ class ReinforceAgent:
         """(obs code, hidden sizes, activation code, int32 ctypes array of the sizes) when the net is covered by the
         any-depth kernels of g2048_deep.hip (1..4 hidden layers of 1..256 units, ReLU / Sigmoid, fp32 on this
         device, log2 / raw / one-hot obs), else None."""
+        if self._sized:      # input_dim is N*N(*17) here: a 3 x 3 net would otherwise pass the width check below
+            return None
         params = self.params if params is None else params
         Ws, bs = params["W"], params["b"]
         nh = len(Ws) - 1
@@ -517,7 +543,7 @@ class ReinforceAgent:
     def _onehot_first_layer(self, steps: "_Steps") -> bool:
         """The batched update gathers the one-hot first layer from the bitboards (g2048_onehot_layer1 /
         g2048_onehot_dw1) instead of materialising [m, 272] one-hot obs for 272-wide GEMMs."""
-        return steps.boards is not None and self.env_config.obs_mode == "onehot"
+        return steps.boards is not None and self.env_config.obs_mode == "onehot" and not self._sized
 
     def _mask_from_boards(self, boards: torch.Tensor) -> torch.Tensor:
         m = boards.numel()
@@ -1166,7 +1192,8 @@ class ReinforceAgent:
             dspec = None
         self._paths["rollout"] = ("g2048_policy + g2048_step per step (active lanes)" if spec is not None else
                                   "g2048_deep_policy + g2048_step per step (active lanes)" if dspec is not None else
-                                  "hipBLASLt forward (active lanes) + g2048_sample + g2048_step per step")
+                                  "hipBLASLt forward (active lanes) + g2048_sample + " +
+                                  ("g2048_sized_step" if self._sized else "g2048_step") + " per step")
         env = self._vec_env(n, rng)
         env.reset(seed=_seed_seq(env_seeds))
         dev = self.device
@@ -1182,7 +1209,10 @@ class ReinforceAgent:
         ms = self.env_config.max_steps
         cap = int(ms) if (ms is not None and ms > 0) else 1024
         cap = max(cap, 1)
-        boards = torch.empty(cap, n, dtype=torch.int64, device=dev)
+        # sizes other than 4: [W, cap, n] planes; row t is the view boards[:, t] (plane stride cap * n)
+        bshape = (lambda rows: (env.words, rows, n)) if self._sized else (lambda rows: (rows, n))
+        row_of = (lambda b, t: b[:, t]) if self._sized else (lambda b, t: b[t])
+        boards = torch.empty(bshape(cap), dtype=torch.int64, device=dev)
         actions = torch.empty(cap, n, dtype=torch.uint8, device=dev)
         rewards = torch.zeros(cap, n, dtype=torch.float64, device=dev)
         flags = torch.empty(cap, n, dtype=torch.uint8, device=dev)
@@ -1200,7 +1230,8 @@ class ReinforceAgent:
         while True:
             if t == cap:
                 grow = cap
-                boards = torch.cat([boards, torch.empty(grow, n, dtype=torch.int64, device=dev)])
+                boards = torch.cat([boards, torch.empty(bshape(grow), dtype=torch.int64, device=dev)],
+                                   dim=1 if self._sized else 0)
                 actions = torch.cat([actions, torch.empty(grow, n, dtype=torch.uint8, device=dev)])
                 rewards = torch.cat([rewards, torch.zeros(grow, n, dtype=torch.float64, device=dev)])
                 flags = torch.cat([flags, torch.empty(grow, n, dtype=torch.uint8, device=dev)])
@@ -1239,7 +1270,7 @@ class ReinforceAgent:
                                                L.ptr(pinc), L.ptr(pbuf), env.philox_key ^ 0x5A5A, L.ptr(pseeds),
                                                L.ptr(probs[t]) if probs is not None else None,
                                                L.ptr(actions[t]), n, self._stream))
-                env.step_into(actions[t], reward=env.reward, flags=flags[t], prev_board=boards[t],
+                env.step_into(actions[t], reward=env.reward, flags=flags[t], prev_board=row_of(boards, t),
                               reward64=rewards[t])
             total += rewards[t]      # inactive lanes got reward 0.0
             t += 1
@@ -1248,8 +1279,8 @@ class ReinforceAgent:
         fl = flags[:t]
         lengths = ((fl & L.F_INACTIVE) == 0).sum(0).to(torch.int32)
         T = int(lengths.max().item()) if n else 0
-        return TrajectoryBatch(boards=boards[:T], actions=actions[:T], rewards=rewards[:T],
-                               flags=fl[:T], lengths=lengths, total_reward=total,
+        return TrajectoryBatch(boards=boards[:, :T] if self._sized else boards[:T], actions=actions[:T],
+                               rewards=rewards[:T], flags=fl[:T], lengths=lengths, total_reward=total,
                                max_tile=env.max_tile_seen.clone(), final_boards=env.board.clone(),
                                probs=probs[:T] if probs is not None else None)
 
@@ -1385,16 +1416,26 @@ class ReinforceAgent:
     def trajectories_from_batch(self, batch: TrajectoryBatch, with_states: bool = True) -> list[dict[str, Any]]:
         """Convert a device batch to the reference's trajectory dicts (src/reinforce_agent.py:240-247)."""
         n, T = batch.n, batch.T
-        x, mk = self._obs_from_boards(batch.boards.reshape(-1).contiguous())
+        N = self.size
+        if self._sized:
+            from .vec_env import sized_exponents
+
+            x, mk = self._obs_from_boards(batch.boards.reshape(batch.boards.shape[0], -1).contiguous())
+            ex = sized_exponents(batch.boards, N).cpu().numpy()                     # [T, n, N, N]
+            values = np.where(ex > 0, np.left_shift(np.int64(1), ex), 0).astype(np.int64)
+            board_values = lambda t, i: values[t, i]                                 # noqa: E731
+        else:
+            x, mk = self._obs_from_boards(batch.boards.reshape(-1).contiguous())
+            boards = batch.boards.cpu().numpy().view(np.uint64)
+            board_values = lambda t, i: _board_values(int(boards[t, i]))             # noqa: E731
         x = x.view(T, n, -1).cpu().numpy()
         mk = mk.view(T, n, 4).cpu().numpy()
-        boards = batch.boards.cpu().numpy().view(np.uint64)
         acts = batch.actions.cpu().numpy()
         rews = batch.rewards.cpu().numpy()
         lens = batch.lengths.cpu().numpy()
         tot = batch.total_reward.cpu().numpy()
         mt = batch.max_tile.cpu().numpy()
-        shape = (4, 4, 17) if self.input_dim == 272 else (4, 4)
+        shape = (N, N, 17) if self.env_config.obs_mode == "onehot" else (N, N)
         out = []
         for i in range(n):
             Ti = int(lens[i])
@@ -1405,7 +1446,7 @@ class ReinforceAgent:
                            else board)
             traj = {"obs": obs, "actions": [int(a) for a in acts[:Ti, i]],
                     "rewards": [float(r) for r in rews[:Ti, i]], "total_reward": float(tot[i]),
-                    "states": [_render_values(_board_values(int(b))) for b in boards[:Ti, i]] if with_states else [],
+                    "states": [_render_values(board_values(t, i)) for t in range(Ti)] if with_states else [],
                     "max_tile": int(mt[i])}
             out.append(traj)
         return out

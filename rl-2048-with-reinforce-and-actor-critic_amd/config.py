@@ -39,17 +39,32 @@ class Game2048EnvConfig:
     max_steps: int | None = 1024
 
 
-def obs_width(obs_mode: str) -> int:
+MIN_SIZE, MAX_SIZE = 2, 8
+
+
+def check_size(size) -> int:
+    """Game2048EnvConfig.size as an int in 2..8 (the sizes the device boards cover), else ValueError."""
+    if isinstance(size, bool) or not isinstance(size, int) or not MIN_SIZE <= size <= MAX_SIZE:
+        raise ValueError(f"board size must be an integer in {MIN_SIZE}..{MAX_SIZE} (got {size!r})")
+    return size
+
+
+def board_words(size: int) -> int:
+    """uint64 words of one size x size board (16 cells per word)."""
+    return (check_size(size) ** 2 + 15) // 16
+
+
+def obs_width(obs_mode: str, size: int = 4) -> int:
     if obs_mode not in _OBS:
         raise ValueError(f"Unsupported obs_mode: {obs_mode}")
-    return 272 if obs_mode == "onehot" else 16
+    cells = check_size(size) ** 2
+    return cells * 17 if obs_mode == "onehot" else cells
 
 
 def env_cfg_struct(cfg: Game2048EnvConfig) -> L.EnvCfg:
     """Validate and convert.  Raises ValueError with the reference's messages (src/env.py:110,223,249);
     the reference raises the reward/bonus ones lazily at the first step, this build at construction."""
-    if cfg.size != 4:
-        raise ValueError("only size=4 boards are supported (uint64 bitboard)")
+    check_size(cfg.size)     # size is not part of the C struct: it is an argument of the sized entry points
     if cfg.obs_mode not in _OBS:
         raise ValueError(f"Unsupported obs_mode: {cfg.obs_mode}")
     if cfg.reward_mode not in _REWARD:

@@ -14,8 +14,8 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from .config import Game2048EnvConfig
-from .vec_env import VecGame2048Env, decode_merged
+from .config import Game2048EnvConfig, check_size
+from .vec_env import VecGame2048Env, decode_merged, decode_merged_sized
 
 Action = int  # 0:up, 1: right, 2: down, 3: left
 
@@ -50,26 +50,52 @@ def _values(b: int) -> np.ndarray:
     return np.where(e > 0, np.left_shift(np.int64(1), e), 0).astype(np.int64)
 
 
+class Box:
+    """The slice of gymnasium.spaces.Box the reference's observation spaces use (src/env.py:79-128)."""
+
+    def __init__(self, low, high, shape, dtype):
+        self.low, self.high, self.shape, self.dtype = low, high, tuple(shape), dtype
+
+
+class Dict:
+    """gymnasium.spaces.Dict as a plain mapping of sub-spaces."""
+
+    def __init__(self, spaces: dict):
+        self.spaces = dict(spaces)
+
+    def __getitem__(self, key):
+        return self.spaces[key]
+
+
+def _lane_state(vec: VecGame2048Env):
+    """Lane 0's board values [N,N], score, flags and merged list (tile values) in one small copy each."""
+    ints = torch.stack([vec.score.to(torch.int64), vec.flags.to(torch.int64), vec.max_tile.to(torch.int64),
+                        vec.step_count.to(torch.int64)]).cpu()
+    score, flags, mt, sc = [int(x) for x in ints[:, 0].tolist()]
+    if vec.size == 4:
+        both = torch.stack([vec.board, vec.merged.to(torch.int64)]).cpu()
+        board = _values(int(both[0, 0]) & 0xFFFFFFFFFFFFFFFF)
+        merged = decode_merged(int(both[1, 0]))
+    else:
+        board = vec.boards_values()[0].cpu().numpy().astype(np.int64)
+        merged = decode_merged_sized(vec.merged[0].cpu())
+    return board, score, flags, merged, mt, sc
+
+
 class Game2048:
     """src/game2048.py:Game2048 on one device lane.  Tile values are exact up to 2**15; a 2**15+2**15
     merge saturates on the board (``overflow`` becomes True) while step()'s merged list and score stay exact."""
 
     def __init__(self, size: int = 4, device=None):
-        if size != 4:
-            raise ValueError("only size=4 boards are supported")
-        self.size = size
-        self._vec = VecGame2048Env(1, Game2048EnvConfig(max_steps=None), device=device, record_merged=True)
-        self._host_board = np.zeros((4, 4), dtype=np.int64)
+        self.size = check_size(size)
+        self._vec = VecGame2048Env(1, Game2048EnvConfig(size=size, max_steps=None), device=device, record_merged=True)
+        self._host_board = np.zeros((size, size), dtype=np.int64)
         self.step_count = 0
         self.score = 0
         self.overflow = False
 
     def _pull(self) -> None:
-        vals = torch.stack([self._vec.board, self._vec.score.to(torch.int64),
-                            self._vec.flags.to(torch.int64), self._vec.merged.to(torch.int64)]).cpu().tolist()
-        b, score, flags, merged = [int(v[0]) for v in vals]
-        self._host_board = _values(b & 0xFFFFFFFFFFFFFFFF)
-        self.score = score
+        self._host_board, self.score, flags, merged, _, _ = _lane_state(self._vec)
         return flags, merged
 
     @property
@@ -98,7 +124,7 @@ class Game2048:
         # reference never stops a finished game), so re-activate it
         if flags & L.F_TERMINATED:
             self._vec.set_active()
-        return bool(flags & L.F_CHANGED), self.state, decode_merged(merged), bool(flags & L.F_TERMINATED)
+        return bool(flags & L.F_CHANGED), self.state, merged, bool(flags & L.F_TERMINATED)
 
     def get_action_mask(self) -> list[int]:
         return [int(x) for x in self._vec.mask[0].cpu().tolist()]
@@ -119,8 +145,22 @@ class Game2048Env:
         self.action_space = Discrete(4)
         self._step_count = 0
         self.max_tile_seen = 4
-        self._board = np.zeros((4, 4), dtype=np.int64)
+        self._board = np.zeros((self.config.size, self.config.size), dtype=np.int64)
         self._score = 0
+        self.observation_space = self._build_observation_space()
+
+    def _build_observation_space(self):
+        """src/env.py:79-128: the board Box shaped by config.size (and the mask Box under use_action_mask)."""
+        size = self.config.size
+        if self.config.obs_mode == "raw":
+            board_space = Box(0, 2 ** self._max_num, (size, size), np.float32)
+        elif self.config.obs_mode == "log2":
+            board_space = Box(0.0, self._max_num, (size, size), np.float32)
+        else:
+            board_space = Box(0.0, 1.0, (size, size, int(self._max_num) + 1), np.float32)
+        if self.config.use_action_mask:
+            return Dict({"board": board_space, "action_mask": Box(0, 1, (self.action_space.n,), np.int8)})
+        return board_space
 
     # -------------------------------------------------------------------------------------------- helpers
     @property
@@ -129,19 +169,18 @@ class Game2048Env:
 
     def _sync(self):
         v = self._vec
-        ints = torch.stack([v.board, v.score.to(torch.int64), v.flags.to(torch.int64), v.merged.to(torch.int64),
-                            v.max_tile.to(torch.int64), v.step_count.to(torch.int64)]).cpu()
-        b, score, flags, merged, mt, sc = [int(x) for x in ints[:, 0].tolist()]
+        board, score, flags, merged, mt, sc = _lane_state(v)
         obs = v.obs[0].cpu().numpy().copy()
         mask = v.mask[0].cpu().numpy().copy()
         reward = float(v.reward64[0].item())    # fp64, as src/env.py:261 returns it
-        self._board = _values(b & 0xFFFFFFFFFFFFFFFF)
+        self._board = board
         self._score = score
         self.max_tile_seen = 1 << mt
         return obs, mask, reward, flags, merged
 
     def _obs(self, obs: np.ndarray, mask: np.ndarray):
-        board = obs.reshape(4, 4, 17) if obs.size == 272 else obs.reshape(4, 4)
+        N = self.config.size
+        board = obs.reshape(N, N, 17) if self.config.obs_mode == "onehot" else obs.reshape(N, N)
         if self.config.use_action_mask:
             return {"board": board, "action_mask": mask.astype(np.int8)}
         return board
@@ -164,7 +203,7 @@ class Game2048Env:
         invalid = bool(flags & L.F_INVALID)
         if terminated or truncated:
             self._vec.set_active()  # the reference env keeps stepping after the end if asked to
-        info = {"score": self._score, "raw_state": self.state, "merged": decode_merged(merged),
+        info = {"score": self._score, "raw_state": self.state, "merged": merged,
                 "invalid_action": invalid, "step_index": self._step_count}
         return self._obs(obs, mask), float(reward), terminated, truncated, info
 

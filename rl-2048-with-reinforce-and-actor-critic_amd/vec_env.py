@@ -18,7 +18,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from .config import Game2048EnvConfig, env_cfg_struct, obs_width
+from .config import Game2048EnvConfig, board_words, check_size, env_cfg_struct, obs_width
 
 
 def _signed64(v: int) -> int:
@@ -79,6 +79,11 @@ class VecGame2048Env:
     ``status`` and ``active`` are views computed from it.
     packed_mask: the steps write the action mask as one byte per lane (``mask_bits``, bit a = action a) instead
     of int8[4] -- 3 B less per board-step; ``obs["action_mask"]`` is then unpacked from it on access.
+
+    config.size = N in 2..8.  N = 4 is the product path (one uint64 per board, row tables, everything above).  Any
+    other N runs the sized kernels (g2048_sized_*): ``board`` is int64 [W, n] (plane-major, W = ceil(N*N/16) words,
+    cell r*N+c in nibble (r*N+c) & 15 of word (r*N+c) >> 4), ``prev_board`` likewise, obs [n,N,N(,17)], and
+    ``merged`` uint8 [n, N*(N//2)] (exponents in list order, 0-terminated: decode_merged_sized).
     """
 
     def __init__(self, num_envs: int, config: Game2048EnvConfig | None = None, device=None, rng: str = "pcg64",
@@ -89,6 +94,9 @@ class VecGame2048Env:
             raise ValueError("num_envs must be positive")
         self.config = config or Game2048EnvConfig()
         self._cfg = env_cfg_struct(self.config)          # validates modes (ValueError like src/env.py:110,223,249)
+        self.size = check_size(self.config.size)
+        self.words = board_words(self.size)
+        self._sized = self.size != 4                     # 4 x 4 never routes through the sized entry points
         self.n = int(num_envs)
         if rng not in ("pcg64", "philox"):
             raise ValueError(f"Unsupported rng: {rng}")
@@ -107,7 +115,7 @@ class VecGame2048Env:
         n, dev = self.n, self.device
         z = lambda dt, *s: torch.zeros(*s, dtype=dt, device=dev)  # noqa: E731
         # lane state (g2048_lanes)
-        self.board = z(torch.int64, n)
+        self.board = z(torch.int64, self.words, n) if self._sized else z(torch.int64, n)
         self.state = z(torch.int32, n)                   # G2048_LS_* word (uint32 bits in an int32 tensor)
         self.seed = z(torch.int64, n)
         pcg = self.rng_mode == L.RNG_PCG64
@@ -123,21 +131,42 @@ class VecGame2048Env:
         self.flags = z(torch.uint8, n)
         self.mask = z(torch.int8, n, 4)                  # written by reset (and by steps unless packed_mask)
         self.mask_bits = z(torch.uint8, n) if packed_mask else None
-        self.obs_width = obs_width(self.config.obs_mode)
+        self.obs_width = obs_width(self.config.obs_mode, self.size)
         self.obs = z(torch.float32, n, self.obs_width)
-        self.merged = z(torch.int32, n) if record_merged else None
-        self.prev_board = z(torch.int64, n) if record_prev_board else None
+        if self._sized:
+            self.merged = z(torch.uint8, n, self.size * (self.size // 2)) if record_merged else None
+            self.prev_board = z(torch.int64, self.words, n) if record_prev_board else None
+        else:
+            self.merged = z(torch.int32, n) if record_merged else None
+            self.prev_board = z(torch.int64, n) if record_prev_board else None
         self._lanes = L.Lanes(*[L.ptr(t) for t in (self.board, self.state, self.seed, self.rng_state, self.rng_inc,
                                                    self.rng_uint)])
-        self._out = L.StepOut(L.ptr(self.reward), L.ptr(self.flags), self._mask_ptr(), L.ptr(self.obs),
-                              L.ptr(self.merged), L.ptr(self.prev_board), L.ptr(self.reward64), L.ptr(self._score_add),
-                              L.ptr(self.mask_bits))
+        if self._sized:
+            self._out = self._sized_out(self.reward, self.flags, self.prev_board, True, self.reward64)
+        else:
+            self._out = L.StepOut(L.ptr(self.reward), L.ptr(self.flags), self._mask_ptr(), L.ptr(self.obs),
+                                  L.ptr(self.merged), L.ptr(self.prev_board), L.ptr(self.reward64),
+                                  L.ptr(self._score_add), L.ptr(self.mask_bits))
         self._lib = L.lib()
         self._stream = L.stream_handle(self.device)
 
     # ------------------------------------------------------------------------------------------------------
     def _mask_ptr(self):
         return None if self.mask_bits is not None else L.ptr(self.mask)
+
+    def _sized_out(self, reward, flags, prev_board, write_obs, reward64) -> L.SizedStepOut:
+        """g2048_sized_step_out.  prev_board: int64 [W, n] planes whose rows are contiguous; the plane stride may
+        exceed n (row t of a [W, cap, n] trajectory tensor: traj[:, t])."""
+        pstride = self.n
+        if prev_board is not None:
+            if (prev_board.dtype != torch.int64 or prev_board.device != self.device
+                    or tuple(prev_board.shape) != (self.words, self.n) or prev_board.stride(1) != 1):
+                raise ValueError(f"prev_board must be an int64 [{self.words}, {self.n}] tensor of contiguous planes "
+                                 "on the env device")
+            pstride = prev_board.stride(0) if self.words > 1 else self.n
+        return L.SizedStepOut(L.ptr(reward), L.ptr(flags), self._mask_ptr(), L.ptr(self.obs) if write_obs else None,
+                              L.ptr(self.merged), None if prev_board is None else prev_board.data_ptr(),
+                              L.ptr(reward64), L.ptr(self._score_add), L.ptr(self.mask_bits), pstride)
 
     @property
     def action_mask(self) -> torch.Tensor:
@@ -148,7 +177,8 @@ class VecGame2048Env:
         return ((self.mask_bits.unsqueeze(1) & bits) != 0).to(torch.int8)
 
     def _obs_view(self):
-        board = self.obs.view(self.n, 4, 4, 17) if self.obs_width == 272 else self.obs.view(self.n, 4, 4)
+        N = self.size
+        board = self.obs.view(self.n, N, N, 17) if self.config.obs_mode == "onehot" else self.obs.view(self.n, N, N)
         if self.config.use_action_mask:
             return {"board": board, "action_mask": self.action_mask}
         return board
@@ -161,9 +191,16 @@ class VecGame2048Env:
         if mask is not None:
             m = mask.to(device=self.device, dtype=torch.uint8).contiguous()
         with torch.cuda.device(self.device):
-            L.check(self._lib.g2048_reset(ctypes.byref(self._lanes), L.ptr(seeds), L.ptr(m), ctypes.byref(self._cfg),
-                                          self.rng_mode, self.philox_key, L.ptr(self.mask), L.ptr(self.obs), self.n,
-                                          L.stream_handle(self.device)))
+            if self._sized:
+                L.check(self._lib.g2048_sized_reset(self.size, ctypes.byref(self._lanes), self.n, L.ptr(seeds),
+                                                    L.ptr(m), ctypes.byref(self._cfg), self.rng_mode, self.philox_key,
+                                                    L.ptr(self.mask), L.ptr(self.obs), self.n,
+                                                    L.stream_handle(self.device)))
+            else:
+                L.check(self._lib.g2048_reset(ctypes.byref(self._lanes), L.ptr(seeds), L.ptr(m),
+                                              ctypes.byref(self._cfg), self.rng_mode, self.philox_key,
+                                              L.ptr(self.mask), L.ptr(self.obs), self.n,
+                                              L.stream_handle(self.device)))
         if self.score is not None:
             if m is None:
                 self.score.zero_()
@@ -189,7 +226,14 @@ class VecGame2048Env:
         if actions.dtype != torch.uint8 or actions.device != self.device or actions.numel() != self.n:
             raise ValueError("actions must be a uint8 tensor of num_envs elements on the env device")
         out = self._out
-        if reward is not None or flags is not None or prev_board is not None or not write_obs or reward64 is not None:
+        custom = (reward is not None or flags is not None or prev_board is not None or not write_obs
+                  or reward64 is not None)
+        if custom and self._sized:
+            out = self._sized_out(reward if reward is not None else self.reward,
+                                  flags if flags is not None else self.flags,
+                                  prev_board if prev_board is not None else self.prev_board, write_obs,
+                                  reward64 if reward64 is not None else self.reward64)
+        elif custom:
             out = L.StepOut(L.ptr(reward if reward is not None else self.reward),
                             L.ptr(flags if flags is not None else self.flags), self._mask_ptr(),
                             L.ptr(self.obs) if write_obs else None,
@@ -199,9 +243,15 @@ class VecGame2048Env:
         if torch.cuda.current_device() != self.device.index:
             with torch.cuda.device(self.device):
                 return self.step_into(actions, reward, flags, prev_board, write_obs, reward64)
-        L.check(self._lib.g2048_step(ctypes.byref(self._lanes), L.ptr(actions), ctypes.byref(self._cfg),
-                                     ctypes.byref(out), self.rng_mode, self.philox_key, int(self.auto_reset),
-                                     self.reset_stride, self.n, L.stream_handle(self.device)))
+        if self._sized:
+            L.check(self._lib.g2048_sized_step(self.size, ctypes.byref(self._lanes), self.n, L.ptr(actions),
+                                               ctypes.byref(self._cfg), ctypes.byref(out), self.rng_mode,
+                                               self.philox_key, int(self.auto_reset), self.reset_stride, self.n,
+                                               L.stream_handle(self.device)))
+        else:
+            L.check(self._lib.g2048_step(ctypes.byref(self._lanes), L.ptr(actions), ctypes.byref(self._cfg),
+                                         ctypes.byref(out), self.rng_mode, self.philox_key, int(self.auto_reset),
+                                         self.reset_stride, self.n, L.stream_handle(self.device)))
         if self.score is not None:   # Game2048.score += sum(merged); an auto-reset lane starts its new game at 0
             fl = flags if flags is not None else self.flags
             self.score.add_(self._score_add).masked_fill_((fl & L.F_RESET) != 0, 0)
@@ -224,7 +274,7 @@ class VecGame2048Env:
                 "invalid_action": (f & L.F_INVALID) != 0, "step_index": self.step_count,
                 "reset": (f & L.F_RESET) != 0, "overflow": (f & L.F_OVERFLOW) != 0}
         if self.merged is not None:
-            info["merged_packed"] = self.merged
+            info["merged_bytes" if self._sized else "merged_packed"] = self.merged
         rew = self.reward64 if self.reward64 is not None else self.reward
         return (self._obs_view(), rew, (f & L.F_TERMINATED) != 0, (f & L.F_TRUNCATED) != 0, info)
 
@@ -276,7 +326,9 @@ class VecGame2048Env:
         return torch.ones_like(self.state, dtype=torch.int64) << self.max_tile.to(torch.int64)
 
     def boards_exponents(self) -> torch.Tensor:
-        """[n,4,4] int64 exponents (0 = empty) of the current boards."""
+        """[n,N,N] int64 exponents (0 = empty) of the current boards."""
+        if self._sized:
+            return sized_exponents(self.board, self.size)
         b = self.board
         shifts = torch.arange(0, 64, 4, device=self.device, dtype=torch.int64)
         return ((b.unsqueeze(1) >> shifts) & 15).view(self.n, 4, 4)
@@ -295,4 +347,24 @@ def decode_merged(word: int) -> list[int]:
         if nib == 0:
             break
         out.append(1 << (nib + 1))
+    return out
+
+
+def sized_exponents(board: torch.Tensor, size: int) -> torch.Tensor:
+    """Plane-major sized boards int64 [W, ...] -> exponents int64 [..., N, N] (cell k: nibble k & 15 of word k >> 4)."""
+    k = torch.arange(size * size, device=board.device)
+    planes = board[k >> 4]                                        # [N*N, ...]
+    sh = (4 * (k & 15)).view(-1, *([1] * (board.dim() - 1)))
+    e = (planes >> sh) & 15
+    return e.movedim(0, -1).reshape(*board.shape[1:], size, size)
+
+
+def decode_merged_sized(row) -> list[int]:
+    """One lane's g2048_sized_step_out.merged bytes -> the reference's merged list (tile values,
+    src/game2048.py:131): exponents in list order, ended by the first 0 (or the end of the row)."""
+    out = []
+    for e in (row.tolist() if hasattr(row, "tolist") else list(row)):
+        if e == 0:
+            break
+        out.append(1 << int(e))
     return out

@@ -33,7 +33,7 @@ if r.returncode != 0:
     sys.exit(1)
 rows, cur = [], None
 for line in r.stderr.splitlines():
-    m = re.search(r"remark: ([^\[]+?)\s*\[-Rpass", line)
+    m = re.search(r"remark:\s+(.*?)\s*\[-Rpass", line)
     if not m:
         continue
     txt = m.group(1)
