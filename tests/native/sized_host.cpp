@@ -77,15 +77,17 @@ RewardCfg reward_cfg(const EpCfg& c) {
 }
 
 // Game2048Env.reset(seed) + steps on the numpy PCG64 stream.  boards [steps + 1][W] (row 0 = the reset board),
-// lists [steps][kListLen]; per step reward (fp64), flags, score_add, mask, max tile exponent.
+// lists [steps][kListLen]; per step reward (fp64), flags, score_add, mask, max tile exponent.  start (W words, or
+// NULL): a board that replaces the reset board before the first step (the stream stays where reset left it).
 template <int N>
-void t_episode(uint64_t seed, const uint8_t* actions, int64_t steps, const EpCfg* cfg, uint64_t* boards,
+void t_episode(uint64_t seed, const uint64_t* start, const uint8_t* actions, int64_t steps, const EpCfg* cfg, uint64_t* boards,
                uint8_t* lists, double* rewards, uint32_t* flags, uint32_t* score_add, uint32_t* masks,
                uint32_t* max_tile, uint32_t* reset_mask) {
     constexpr int W = sz::Dim<N>::kWords, LEN = sz::Dim<N>::kListLen;
     const RewardCfg rc = reward_cfg(*cfg);
     Pcg64 g;
     sz::Board<N> b = sz::fresh_board<N, 0>(seed, 0, g);
+    if (start) b = from_words<N>(start);
     to_words<N>(b, boards);
     *reset_mask = sz::action_mask<N>(b);
     uint32_t mt = 2;
@@ -372,8 +374,20 @@ void sh_fresh_philox(int size, uint64_t key, uint64_t seed, uint64_t* out) {
 void sh_episode(int size, uint64_t seed, const uint8_t* actions, int64_t steps, const EpCfg* cfg, uint64_t* boards,
                 uint8_t* lists, double* rewards, uint32_t* flags, uint32_t* score_add, uint32_t* masks,
                 uint32_t* max_tile, uint32_t* reset_mask) {
-#define CALL(NN) \
-    t_episode<NN>(seed, actions, steps, cfg, boards, lists, rewards, flags, score_add, masks, max_tile, reset_mask)
+#define CALL(NN)                                                                                              \
+    t_episode<NN>(seed, nullptr, actions, steps, cfg, boards, lists, rewards, flags, score_add, masks, max_tile, \
+                  reset_mask)
+    SIZED_SWITCH(size, CALL)
+#undef CALL
+}
+
+// sh_episode from an injected board: reset(seed), the board overwritten with `start`, then the steps
+void sh_episode_from(int size, uint64_t seed, const uint64_t* start, const uint8_t* actions, int64_t steps,
+                     const EpCfg* cfg, uint64_t* boards, uint8_t* lists, double* rewards, uint32_t* flags,
+                     uint32_t* score_add, uint32_t* masks, uint32_t* max_tile, uint32_t* reset_mask) {
+#define CALL(NN)                                                                                            \
+    t_episode<NN>(seed, start, actions, steps, cfg, boards, lists, rewards, flags, score_add, masks, max_tile, \
+                  reset_mask)
     SIZED_SWITCH(size, CALL)
 #undef CALL
 }

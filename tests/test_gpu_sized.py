@@ -3,6 +3,10 @@ tests/golden/sized.npz, recorded from the real reference by tests/golden/make_go
 observations, merged lists, scores and the fp64 reward are compared for equality (the reward with ==).
 
 Lane counts 1, 63 and 257: below a wave, and one past a 256-thread workgroup.  Lane i replays fixture episode i % E.
+
+sized.npz is random play from reset, cut at 60 steps for N >= 5: early-game states only.  Late-game states -- full
+and nearly full boards, termination, tiles of 2^8 .. 2^15, saturated merges, a full merged list, the Lemire fallback,
+auto-reset after termination -- are in tests/test_gpu_sized_late.py.
 """
 import ctypes
 import json
@@ -11,6 +15,8 @@ import os
 import numpy as np
 import pytest
 import torch
+
+from sized_ref import as_sized4 as _as_sized4   # shared with tests/test_gpu_sized_late.py
 
 pytestmark = pytest.mark.gpu
 
@@ -143,16 +149,6 @@ def test_vec_env_matches_reference_episodes(gold, lib, n, c, lanes):
     pv[1:] &= v[:-1]
     assert np.array_equal(prev[pv], want_prev[pv])
 
-
-def _as_sized4(env, L):
-    """Re-point a size-4 env at the sized entry points (W = 1): same buffers, the sized output struct."""
-    n = env.n
-    env._sized = True
-    env.board = env.board.view(1, n)
-    env.merged = torch.zeros(n, 8, dtype=torch.uint8, device=DEV)
-    env.prev_board = torch.zeros(1, n, dtype=torch.int64, device=DEV)
-    env._out = env._sized_out(env.reward, env.flags, env.prev_board, True, env.reward64)
-    return env
 
 
 @pytest.mark.parametrize("rng,c", [("pcg64", 2), ("philox", 3), ("pcg64", 1)])

@@ -75,6 +75,8 @@ def sh():
     L.sh_fresh_philox.argtypes = [ctypes.c_int, ctypes.c_uint64, ctypes.c_uint64, u64p]
     L.sh_episode.argtypes = [ctypes.c_int, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_int64, ctypes.POINTER(EpCfg)] + \
         [ctypes.c_void_p] * 7 + [u32p]
+    L.sh_episode_from.argtypes = [ctypes.c_int, ctypes.c_uint64, u64p, ctypes.c_void_p, ctypes.c_int64,
+                                  ctypes.POINTER(EpCfg)] + [ctypes.c_void_p] * 7 + [u32p]
     L.sh_selfcheck.restype = ctypes.c_int64
     L.sh_selfcheck.argtypes = [ctypes.c_int, ctypes.c_int64, ctypes.c_uint64]
     L.sh_check_n4.restype = ctypes.c_int64
