@@ -24,7 +24,14 @@ extern "C" {
  * counterparts.  obs buffers are [n * N*N] (raw / log2) or [n * N*N*17] (one-hot, channel e of cell r*N+c at
  * (r*N+c)*17 + e) and must be 16-byte aligned.  Every entry point accepts N = 4 too (W = 1, same results as the 4 x 4
  * entry points; the product path does not use them).  A size outside 2..8, a plane_stride below the lanes it must
- * hold or n > 2^30 return G2048_EINVAL before any launch. */
+ * hold or n > 2^30 return G2048_EINVAL before any launch.
+ *
+ * The fused policy (g2048_sized_policy.hip; additive, ABI still 17): g2048_sized_policy is g2048_deep_policy for
+ * these boards -- forward of 1..G2048_DEEP_MAX_HIDDEN hidden layers of 1..256 units on raw / log2 / one-hot obs,
+ * masked softmax and the action choice, straight from the board planes (no obs buffer, no GEMM) -- on a net packed
+ * by g2048_sized_pack.  Only layer 0 depends on the size: N*N features (raw / log2) or N*N cells of 17 one-hot
+ * features against W_0's three exact bf16 planes, accumulated cell by cell; at N = 4 the results are
+ * g2048_deep_policy's bit for bit. */
 int g2048_sized_words(int size);   /* W, or -1 for an unsupported size */
 
 /* g2048_step_out for sized boards: the same fields, except */
@@ -62,6 +69,29 @@ int g2048_sized_move(int size, const uint64_t* boards, int64_t plane_stride, con
  * (out_stride >= 8n); out_actions [8n] symmetry-major (NULL ok). */
 int g2048_sized_symmetries(int size, const uint64_t* boards, int64_t plane_stride, const uint8_t* actions,
                            uint64_t* out_boards, int64_t out_stride, uint8_t* out_actions, int64_t n, void* stream);
+
+
+/* Floats in the packed net of g2048_sized_pack, or -1 when the shape is not covered (size 2..8; obs_mode raw, log2 or
+ * one-hot; 1..G2048_DEEP_MAX_HIDDEN hidden layers of 1..256 units).  Host arithmetic only: it never touches the
+ * device. */
+int g2048_sized_policy_packed_size(int size, int obs_mode, int n_hidden, const int32_t* hidden);
+/* g2048_deep_pack for size N: W_l [in, out] row-major (the reference layout), W_0 with N*N rows (raw / log2) or
+ * N*N*17 rows (one-hot: row 17 k + e = cell k = r*N + c, exponent e); out_dim 4 (actor) or 1 (a value head, packed
+ * as output 0). */
+int g2048_sized_pack(int size, const float* const* W, const float* const* b, int obs_mode, int n_hidden,
+                     const int32_t* hidden, int out_dim, float* packed, int64_t packed_len, void* stream);
+/* g2048_deep_policy for size N on plane-major boards (word w of lane i at boards[w * plane_stride + i]); every other
+ * argument and rule is g2048_deep_policy's: lane_index compaction (entry j -> lane lane_index[j]), lane_state
+ * (lanes without G2048_LS_ACTIVE are left untouched; the Philox counter is the step count), use_mask, greedy,
+ * rng_mode PCG64 / Philox, probs_out / logits_out [lanes][4], actions == NULL = forward only (logits_out; a value
+ * head in column 0).  G2048_EINVAL before any launch for a size outside 2..8, plane_stride < n, n > 2^30 or a net
+ * that g2048_sized_policy_packed_size does not cover; n == 0 returns G2048_OK without a launch. */
+int g2048_sized_policy(int size, const float* packed, int n_hidden, const int32_t* hidden, int activation,
+                       const uint64_t* boards, int64_t plane_stride, const uint32_t* lane_state,
+                       const int32_t* lane_index, int obs_mode, float obs_scale, int use_mask, int greedy, int rng_mode,
+                       uint64_t* rng_state, const uint64_t* rng_inc, const uint64_t* rng_buf, uint64_t philox_key,
+                       const uint64_t* lane_seed, float* probs_out, float* logits_out, uint8_t* actions, int64_t n,
+                       void* stream);
 
 #ifdef __cplusplus
 }

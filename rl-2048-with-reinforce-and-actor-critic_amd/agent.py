@@ -261,8 +261,9 @@ class ReinforceAgent:
         if self.env is not None:
             self.env.reset(seed=0)       # the reference probes input_dim this way (src/reinforce_agent.py:70)
         self.size = check_size(self.env_config.size)
-        # sizes other than 4 run the general path only (hipBLASLt forward + g2048_sample + the sized env step, torch
-        # backprop): the fused policy / rollout / gradient kernels read 4 x 4 bitboards and are never offered one
+        # sizes other than 4 run the general path (hipBLASLt forward + g2048_sample + the sized env step, torch
+        # backprop): the fused 4 x 4 policy / rollout / gradient kernels read 4 x 4 bitboards and are never offered one.
+        # Their rollout forward has a fused kernel of its own, g2048_sized_policy (use_fused_sized_policy below)
         self._sized = self.size != 4
         self.input_dim = obs_width(self.env_config.obs_mode, self.size)
         self.n_actions = 4
@@ -286,6 +287,9 @@ class ReinforceAgent:
         self.use_fused_policy = True
         # ... and the whole rollout in one launch (g2048_rollout) when the episodes are bounded (max_steps set)
         self.use_fused_rollout = True
+        # board sizes other than 4: the rollout's forward + choice through g2048_sized_policy (no obs buffer, no GEMM)
+        # when the net fits it (_sized_spec).  Off by default: the general path below stays the product path
+        self.use_fused_sized_policy = False
         # update_batch's actor gradient through the fused g2048_actor_grad kernel when the net fits it (batched path)
         self.use_fused_grad = True
         # two-layer log2 / raw nets through the cooperative g2048_actor_grad / g2048_critic_grad kernels (+ g2048_dw2);
@@ -506,6 +510,53 @@ class ReinforceAgent:
         if any(t.dtype != torch.float32 or t.device != self.device for t in Ws + bs):
             return None
         return (_OBS_CODE[self.env_config.obs_mode], hidden, act, (ctypes.c_int32 * nh)(*hidden))
+
+    def _sized_spec(self, params=None, out_dim: int = 4):
+        """_deep_spec for board sizes other than 4: (obs code, hidden sizes, activation code, int32 ctypes array of
+        the sizes) when g2048_sized_policy covers the net (1..4 hidden layers of 1..256 units, ReLU / Sigmoid, fp32 on
+        this device, W[0] with input_dim = N*N(*17) rows), else None."""
+        if not self._sized:
+            return None
+        params = self.params if params is None else params
+        Ws, bs = params["W"], params["b"]
+        nh = len(Ws) - 1
+        act = {"ReLU": L.ACT_RELU, "Sigmoid": L.ACT_SIGMOID}.get(self.mlp_config.activation)
+        obs_code = _OBS_CODE.get(self.env_config.obs_mode)
+        if act is None or obs_code not in (L.OBS_RAW, L.OBS_LOG2, L.OBS_ONEHOT) or \
+                not (1 <= nh <= L.DEEP_MAX_HIDDEN) or len(bs) != len(Ws):
+            return None
+        hidden = tuple(int(W.shape[1]) for W in Ws[:-1])
+        if tuple(Ws[0].shape)[0] != self.input_dim or tuple(Ws[-1].shape)[1] != out_dim or \
+                not all(1 <= h <= 256 for h in hidden):
+            return None
+        if any(tuple(Ws[l].shape)[0] != hidden[l - 1] for l in range(1, nh + 1)):
+            return None
+        if any(t.dtype != torch.float32 or t.device != self.device for t in Ws + bs):
+            return None
+        harr = (ctypes.c_int32 * nh)(*hidden)
+        if int(self._lib.g2048_sized_policy_packed_size(self.size, obs_code, nh, harr)) < 0:
+            return None
+        return (obs_code, hidden, act, harr)
+
+    def _pack_sized(self, params, sspec, slot: str, out_dim: int) -> torch.Tensor:
+        """g2048_sized_pack of a net, cached per slot until a parameter tensor changes (as _pack_deep)."""
+        Ws, bs = params["W"], params["b"]
+        key = (self._params_version,) + tuple((t.data_ptr(), t._version) for t in Ws + bs)
+        entry = self._pack_cache.setdefault(slot + "/sized", [None, None, None])
+        if key != entry[1]:
+            obs_code, hidden, _, harr = sspec
+            size = int(self._lib.g2048_sized_policy_packed_size(self.size, obs_code, len(hidden), harr))
+            if entry[0] is None or entry[0].numel() < size:
+                entry[0] = torch.empty(size, dtype=torch.float32, device=self.device)
+            ws = [t.contiguous() for t in Ws]
+            bb = [t.contiguous() for t in bs]
+            wp = (ctypes.c_void_p * len(ws))(*[t.data_ptr() for t in ws])
+            bp = (ctypes.c_void_p * len(bb))(*[t.data_ptr() for t in bb])
+            L.check(self._lib.g2048_sized_pack(self.size, wp, bp, obs_code, len(hidden), harr, out_dim,
+                                               L.ptr(entry[0]), size, self._stream))
+            entry[1] = key
+            entry[2] = (ws, bb)      # keep the contiguous copies alive until the (stream-ordered) pack has run
+        return entry[0]
 
     def _pack_deep(self, params, dspec, slot: str, out_dim: int) -> torch.Tensor:
         """g2048_deep_pack of a net, cached per slot until a parameter tensor changes."""
@@ -1190,8 +1241,10 @@ class ReinforceAgent:
             return self._rollout_deep(env_seeds, policy_seeds, dspec, use_greedy, record_probs)
         if spec is not None:
             dspec = None
+        sspec = self._sized_spec() if self.use_fused_sized_policy else None
         self._paths["rollout"] = ("g2048_policy + g2048_step per step (active lanes)" if spec is not None else
                                   "g2048_deep_policy + g2048_step per step (active lanes)" if dspec is not None else
+                                  "g2048_sized_policy + g2048_sized_step per step (active lanes)" if sspec is not None else
                                   "hipBLASLt forward (active lanes) + g2048_sample + " +
                                   ("g2048_sized_step" if self._sized else "g2048_step") + " per step")
         env = self._vec_env(n, rng)
@@ -1224,6 +1277,7 @@ class ReinforceAgent:
         use_mask = bool(self.env_config.use_action_mask)
         packed = self._packed_policy(spec) if spec is not None else None
         dpacked = self._pack_deep(self.params, dspec, "actor", 4) if dspec is not None else None
+        spacked = self._pack_sized(self.params, sspec, "actor", 4) if sspec is not None else None
         logits_buf = None
         active_idx = None
         t = 0
@@ -1242,19 +1296,24 @@ class ReinforceAgent:
             if active_idx is None or t % check_every == 0:
                 active_idx = torch.nonzero(env.active).view(-1).to(torch.int32)
             m = int(active_idx.numel())
-            if spec is not None or dspec is not None:
+            if spec is not None or dspec is not None or sspec is not None:
                 # fused forward + choice straight from the boards; the step then skips the obs buffer
-                common = (L.ptr(env.board), L.ptr(env.state), L.ptr(active_idx) if m < n else None,
+                common = (L.ptr(env.state), L.ptr(active_idx) if m < n else None,
                           _OBS_CODE[self.env_config.obs_mode], float(self.env_config.obs_log2_scale), int(use_mask),
                           int(use_greedy), rng_mode, L.ptr(pst), L.ptr(pinc), L.ptr(pbuf), env.philox_key ^ 0x5A5A,
                           L.ptr(pseeds), L.ptr(probs[t]) if probs is not None else None, None, L.ptr(actions[t]),
                           m if m < n else n, self._stream)
                 if spec is not None:
-                    L.check(self._lib.g2048_policy(L.ptr(packed), spec[0], spec[1], spec[2], *common))
-                else:
-                    L.check(self._lib.g2048_deep_policy(L.ptr(dpacked), len(dspec[1]), dspec[3], dspec[2], *common))
-                env.step_into(actions[t], reward=env.reward, flags=flags[t], prev_board=boards[t], write_obs=False,
-                              reward64=rewards[t])
+                    L.check(self._lib.g2048_policy(L.ptr(packed), spec[0], spec[1], spec[2], L.ptr(env.board),
+                                                   *common))
+                elif dspec is not None:
+                    L.check(self._lib.g2048_deep_policy(L.ptr(dpacked), len(dspec[1]), dspec[3], dspec[2],
+                                                        L.ptr(env.board), *common))
+                else:        # env.board: [W, n] planes
+                    L.check(self._lib.g2048_sized_policy(self.size, L.ptr(spacked), len(sspec[1]), sspec[3], sspec[2],
+                                                         L.ptr(env.board), n, *common))
+                env.step_into(actions[t], reward=env.reward, flags=flags[t], prev_board=row_of(boards, t),
+                              write_obs=False, reward64=rewards[t])
             else:
                 if m < n:
                     # forward only the active lanes; finished lanes are skipped by g2048_sample (lane state)
