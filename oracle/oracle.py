@@ -5,7 +5,8 @@ and only as the checker (or the reported CPU baseline).  The product package nev
 
 ctypes front-end for ``oracle/g2048_oracle.c`` (the literal CPU restatement of src/game2048.py and
 src/env.py plus numpy's PCG64 stream) and small helpers to pack/unpack boards.  The numpy restatement of
-the agent's update math lives in ``oracle/agent_oracle.py``.  Pinning status: see the C file's header and
+the agent's update math lives in ``oracle/agent_oracle.py``.  ``EnvBatch`` steps n oracle envs in one C call
+(OpenMP over lanes) for tests that compare every lane of a large device batch.  Pinning status: see the C file's header and
 DESIGN.md "Oracle".
 """
 from __future__ import annotations
@@ -298,6 +299,140 @@ class Env:
     @property
     def step_count(self) -> int:
         return int(self.e.step_count)
+
+
+class BatchOut(ctypes.Structure):
+    """or_batch_out: one pointer per output array (NULL = not wanted)."""
+    _fields_ = [(name, ctypes.c_void_p) for name in
+                ("reward", "flags", "prev_board", "score_add", "merged", "n_merged", "board", "unrepresentable",
+                 "mask", "obs", "score", "step_count", "max_tile_seen", "seed", "active", "rng_state", "rng_inc",
+                 "has_uint32", "uinteger")]
+
+
+# flag bits of EnvBatch.step()["flags"]
+B_CHANGED, B_TERMINATED, B_TRUNCATED, B_INVALID = 0x01, 0x02, 0x04, 0x08
+B_RESET, B_INACTIVE, B_BADACTION = 0x20, 0x40, 0x80
+
+_BATCH_SYMBOLS = ("or_batch_reset", "or_batch_set_boards", "or_batch_step", "or_batch_state", "or_sizeof_batch_out",
+                  "or_batch_max_threads")
+_batch_ready = False
+
+
+def _batch_lib():
+    """lib() with the batched entry points declared.  A liboracle.so from before they existed says so."""
+    global _batch_ready
+    L = lib()
+    if not _batch_ready:
+        missing = [s for s in _BATCH_SYMBOLS if not hasattr(L, s)]
+        if missing:
+            raise RuntimeError(f"{_LIB_PATH} is an older build without {', '.join(missing)}: rebuild it with "
+                               "`python -c 'import __graft_entry__ as g; g.build()'` (or `make -C oracle`)")
+        vp, i64, u64, P = ctypes.c_void_p, ctypes.c_int64, ctypes.c_uint64, ctypes.POINTER
+        L.or_batch_reset.argtypes = [vp, vp, vp, i64, vp, vp, ctypes.c_int, u64]
+        L.or_batch_reset.restype = None
+        L.or_batch_set_boards.argtypes = [vp, i64, vp, vp]
+        L.or_batch_set_boards.restype = None
+        L.or_batch_step.argtypes = [vp, vp, vp, i64, P(EnvCfg), vp, ctypes.c_int, u64, ctypes.c_int, u64, P(BatchOut)]
+        L.or_batch_step.restype = i64
+        L.or_batch_state.argtypes = [vp, vp, vp, i64, P(EnvCfg), P(BatchOut)]
+        L.or_batch_state.restype = None
+        L.or_batch_max_threads.restype = ctypes.c_int
+        L.or_sizeof_batch_out.restype = ctypes.c_int
+        assert L.or_sizeof_batch_out() == ctypes.sizeof(BatchOut), "struct layout mismatch for BatchOut"
+        _batch_ready = True
+    return L
+
+
+def batch_max_threads() -> int:
+    """Threads the batched loops run on (OpenMP's omp_get_max_threads)."""
+    return int(_batch_lib().or_batch_max_threads())
+
+
+class EnvBatch:
+    """n oracle envs stepped by one C call (OpenMP over lanes): the per-lane ``Env`` above, batched the way the
+    device batches it, so a test can compare every lane of a large batch.  The C side calls the per-lane oracle
+    functions unchanged and adds the device's lane bookkeeping only: inactive lanes (episode over, no
+    auto-reset) and actions > 3 are skipped and flagged; auto-reset restarts the lane with seed += reset_stride
+    in the same step.
+
+    ``step`` / ``state`` return a dict of numpy arrays over lanes.  Step outputs: reward (fp64), flags (B_*),
+    prev_board, score_add, merged [n, 8] (values, list order, zero-filled) and n_merged.  State outputs (the lane
+    after the step and its auto-reset): board (packed u64), unrepresentable (a tile > 2**15: board is not
+    valid), mask (bit a = action a), obs [n, 16 | 272], score, step_count, max_tile_seen, seed, active,
+    rng_state / rng_inc [n, 2] (lo, hi), has_uint32, uinteger.  The arrays are the batch's own buffers: the next
+    call overwrites them.  ``outputs``: the names to compute (default all)."""
+
+    STEP_OUTPUTS = {"reward": (np.float64, ()), "flags": (np.uint8, ()), "prev_board": (np.uint64, ()),
+                    "score_add": (np.int64, ()), "merged": (np.int64, (8,)), "n_merged": (np.int32, ())}
+    STATE_OUTPUTS = {"board": (np.uint64, ()), "unrepresentable": (np.uint8, ()), "mask": (np.uint8, ()),
+                     "obs": (np.float32, None), "score": (np.int64, ()), "step_count": (np.int64, ()),
+                     "max_tile_seen": (np.int64, ()), "seed": (np.uint64, ()), "active": (np.uint8, ()),
+                     "rng_state": (np.uint64, (2,)), "rng_inc": (np.uint64, (2,)), "has_uint32": (np.uint32, ()),
+                     "uinteger": (np.uint32, ())}
+
+    def __init__(self, n: int, rng: str = "pcg64", philox_key: int = 0x2048, auto_reset: bool = False,
+                 reset_stride: int | None = None, outputs=None, **cfg):
+        if rng not in ("pcg64", "philox"):
+            raise ValueError(f"Unsupported rng: {rng}")
+        self._L = _batch_lib()
+        self.n = int(n)
+        self.cfg = make_env_cfg(**cfg)
+        self.philox = int(rng == "philox")
+        self.key = int(philox_key) & 0xFFFFFFFFFFFFFFFF
+        self.auto_reset = int(bool(auto_reset))
+        self.stride = int(self.n if reset_stride is None else reset_stride) & 0xFFFFFFFFFFFFFFFF
+        self._envs = np.zeros(self.n * ctypes.sizeof(EnvState), dtype=np.uint8)
+        self._seed = np.zeros(self.n, dtype=np.uint64)
+        self._active = np.zeros(self.n, dtype=np.uint8)
+        known = {**self.STEP_OUTPUTS, **self.STATE_OUTPUTS}
+        names = list(known) if outputs is None else list(outputs)
+        unknown = [k for k in names if k not in known]
+        if unknown:
+            raise ValueError(f"unknown outputs: {unknown}")
+        self._buf = {}
+        for k in names:
+            dt, tail = known[k]
+            if tail is None:
+                tail = (272 if self.cfg.obs_mode == 2 else 16,)
+            self._buf[k] = np.zeros((self.n,) + tail, dtype=dt)
+        self._out_step = BatchOut(**{k: a.ctypes.data for k, a in self._buf.items()})
+        self._out_state = BatchOut(**{k: a.ctypes.data for k, a in self._buf.items() if k in self.STATE_OUTPUTS})
+
+    def _lanes(self, arr, dtype, what):
+        a = np.ascontiguousarray(arr, dtype=dtype)
+        if a.shape != (self.n,):
+            raise ValueError(f"{what}: expected {self.n} entries, got shape {a.shape}")
+        return a
+
+    def reset(self, seeds, mask=None):
+        """Game2048Env.reset(seed=seeds[i]) of every lane (or those where ``mask`` is nonzero)."""
+        s = self._lanes(seeds, np.uint64, "seeds")
+        m = None if mask is None else self._lanes(mask, np.uint8, "mask")
+        self._L.or_batch_reset(self._envs.ctypes.data, self._seed.ctypes.data, self._active.ctypes.data, self.n,
+                               s.ctypes.data, None if m is None else m.ctypes.data, self.philox,
+                               ctypes.c_uint64(self.key))
+        return self.state()
+
+    def set_boards(self, boards, mask=None):
+        """Overwrite lane boards (packed u64); stream and score kept, step count 0, max_tile_seen 4: what
+        ``env.board.copy_()`` after ``env.reset()`` leaves on the device."""
+        b = self._lanes(boards, np.uint64, "boards")
+        m = None if mask is None else self._lanes(mask, np.uint8, "mask")
+        self._L.or_batch_set_boards(self._envs.ctypes.data, self.n, b.ctypes.data, None if m is None else m.ctypes.data)
+        return self.state()
+
+    def state(self) -> dict:
+        self._L.or_batch_state(self._envs.ctypes.data, self._seed.ctypes.data, self._active.ctypes.data, self.n,
+                               ctypes.byref(self.cfg), ctypes.byref(self._out_state))
+        return {k: a for k, a in self._buf.items() if k in self.STATE_OUTPUTS}
+
+    def step(self, actions) -> dict:
+        a = self._lanes(actions, np.uint8, "actions")
+        self.stepped = int(self._L.or_batch_step(
+            self._envs.ctypes.data, self._seed.ctypes.data, self._active.ctypes.data, self.n, ctypes.byref(self.cfg),
+            a.ctypes.data, self.philox, ctypes.c_uint64(self.key), self.auto_reset, ctypes.c_uint64(self.stride),
+            ctypes.byref(self._out_step)))
+        return dict(self._buf)
 
 
 def obs_of_values(vals, **cfg) -> tuple[np.ndarray, np.ndarray]:
