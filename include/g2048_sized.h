@@ -93,6 +93,30 @@ int g2048_sized_policy(int size, const float* packed, int n_hidden, const int32_
                        const uint64_t* lane_seed, float* probs_out, float* logits_out, uint8_t* actions, int64_t n,
                        void* stream);
 
+/* g2048_deep_rollout for size N (g2048_sized_rollout.hip; additive, ABI still 17): the whole batched rollout in
+ * persistent launches for a net packed by g2048_sized_pack.  The contract is g2048_deep_rollout's: obs mode, obs
+ * scale, use_action_mask, the reward config and max_steps come from cfg; both streams of every episode are numpy
+ * PCG64 (g2048_seed_pcg64); episodes order[0 .. n_order) (NULL: 0 .. n-1, n_order = n) run to their end inside the
+ * launch; one that reaches row cap without ending is suspended -- streams written back into env_* / pol_*, board,
+ * meta and total into *sus, the episode listed in sus->list -- and is resumed by a later call with resume = 1, order
+ * = the suspended list and the trajectory buffers grown (same n, larger cap; rows below the old cap kept).  queue:
+ * one uint32, zero before each call.  A new episode starts from two spawns on an empty board with max tile exponent
+ * 2, step count 0 and total 0.0.
+ * Board buffers are plane-major: traj->boards holds word w of row t of episode e at [w * board_stride + t * n + e]
+ * (board_stride >= cap * n: a [W, cap, n] tensor); traj->final_board and sus->board are [W, n] planes of stride n;
+ * sus->meta and sus->total stay per episode.
+ * max_workgroups: 0 = two workgroups per CU, further capped by ceil(n_order / 32); a positive value caps the grid
+ * below that (a tuning knob: every workgroup runs 32 episode slots that refill from the queue).
+ * G2048_EINVAL before any HIP call for a size outside 2..8, a net g2048_sized_policy_packed_size does not cover,
+ * board_stride < cap * n, bad n / cap / order (g2048_deep_rollout's rules), a NULL required buffer or a negative
+ * max_workgroups; n_order == 0 returns G2048_OK without a launch. */
+int g2048_sized_rollout(int size, const float* packed, int n_hidden, const int32_t* hidden, int activation,
+                        const g2048_env_cfg* cfg, int greedy, uint64_t* env_state, const uint64_t* env_inc,
+                        uint64_t* env_buf, uint64_t* pol_state, const uint64_t* pol_inc, uint64_t* pol_buf,
+                        uint32_t* queue, const int32_t* order, int64_t n_order, int resume, const g2048_suspend* sus,
+                        int64_t n, int64_t cap, const g2048_traj* traj, int64_t board_stride, int max_workgroups,
+                        void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1241,6 +1241,11 @@ class ReinforceAgent:
             return self._rollout_deep(env_seeds, policy_seeds, dspec, use_greedy, record_probs)
         if spec is not None:
             dspec = None
+        if self._sized and self.use_fused_sized_rollout and rng == "pcg64":
+            rspec = self._sized_spec()
+            if rspec is not None:
+                self._paths["rollout"] = "g2048_sized_rollout (persistent launches, suspended episodes resumed)"
+                return self._rollout_sized(env_seeds, policy_seeds, rspec, use_greedy, record_probs)
         sspec = self._sized_spec() if self.use_fused_sized_policy else None
         self._paths["rollout"] = ("g2048_policy + g2048_step per step (active lanes)" if spec is not None else
                                   "g2048_deep_policy + g2048_step per step (active lanes)" if dspec is not None else
@@ -1468,6 +1473,98 @@ class ReinforceAgent:
             cap += grow
         T = int(lengths.max().item()) if n else 0
         return TrajectoryBatch(boards=boards[:T], actions=actions[:T], rewards=rewards[:T], flags=flags[:T],
+                               lengths=lengths, total_reward=totals,
+                               max_tile=torch.ones(n, dtype=torch.int64, device=dev) << max_e.to(torch.int64),
+                               final_boards=final, probs=probs[:T] if probs is not None else None)
+
+    # Board sizes other than 4: the whole rollout through g2048_sized_rollout (persistent launches, as _rollout_deep)
+    # when the net fits it (_sized_spec) and the streams are PCG64.  Off by default: the general path stays the
+    # product path.  A class attribute, so that it can be switched for agents somebody else constructs (the runner).
+    use_fused_sized_rollout = False
+    # its grid cap (0: two workgroups per CU; g2048_sized_rollout's max_workgroups), its first trajectory capacity
+    # (max_steps when that is fewer rows; doubled while episodes run past it) and the most rows it may grow to
+    # (deep_rollout_cap0 / deep_rollout_max_rows for these boards)
+    sized_rollout_max_workgroups = 0
+    sized_rollout_cap0 = 512
+    sized_rollout_max_rows = 1 << 24
+
+    def _rollout_sized(self, env_seeds, policy_seeds, sspec, use_greedy: bool, record_probs: bool) -> TrajectoryBatch:
+        """_rollout_deep for board sizes other than 4 (g2048_sized_rollout): boards are [W, cap, n] planes, final and
+        suspended boards [W, n]; every other buffer, the suspend / grow / resume loop and the refusal are
+        _rollout_deep's.  The batch has the fields, shapes and dtypes of the per-step sized path's."""
+        from .config import env_cfg_struct
+        from .vec_env import _as_u64_seeds
+
+        n = len(env_seeds)
+        dev = self.device
+        W = int(self._lib.g2048_sized_words(self.size))
+        es = _as_u64_seeds(_seed_seq(env_seeds), n, 0, dev)
+        ps = _as_u64_seeds(_seed_seq(policy_seeds), n, 0, dev)
+        streams = []
+        for seeds in (es, ps):
+            st = torch.empty(2 * n, dtype=torch.int64, device=dev)
+            inc = torch.empty(2 * n, dtype=torch.int64, device=dev)
+            buf = torch.empty(n, dtype=torch.int64, device=dev)
+            L.check(self._lib.g2048_seed_pcg64(L.ptr(seeds), L.ptr(st), L.ptr(inc), L.ptr(buf), n, self._stream))
+            streams += [st, inc, buf]
+        ms = self.env_config.max_steps
+        # the first capacity: sized_rollout_cap0 rows, or max_steps when that is fewer (no episode is then suspended)
+        cap = max(min(int(ms), int(self.sized_rollout_cap0)) if ms is not None else int(self.sized_rollout_cap0), 1)
+        boards = torch.empty(W, cap, n, dtype=torch.int64, device=dev)
+        actions = torch.zeros(cap, n, dtype=torch.uint8, device=dev)
+        rewards = torch.zeros(cap, n, dtype=torch.float64, device=dev)
+        flags = torch.full((cap, n), L.F_INACTIVE, dtype=torch.uint8, device=dev)
+        probs = torch.zeros(cap, n, 4, dtype=torch.float32, device=dev) if record_probs else None
+        lengths = torch.empty(n, dtype=torch.int32, device=dev)
+        totals = torch.empty(n, dtype=torch.float64, device=dev)
+        max_e = torch.empty(n, dtype=torch.uint8, device=dev)
+        final = torch.empty(W, n, dtype=torch.int64, device=dev)
+        sus_board = torch.empty(W, n, dtype=torch.int64, device=dev)
+        sus_meta = torch.empty(3 * n, dtype=torch.int32, device=dev)
+        sus_total = torch.empty(n, dtype=torch.float64, device=dev)
+        sus_list = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+        sus_count = torch.zeros(1, dtype=torch.int32, device=dev)
+        sus = L.Suspend(*[L.ptr(t) for t in (sus_board, sus_meta, sus_total, sus_list, sus_count)])
+        queue = torch.zeros(1, dtype=torch.int32, device=dev)
+        cfg = env_cfg_struct(self.env_config)
+        packed = self._pack_sized(self.params, sspec, "actor", 4)
+        _, hidden, act, harr = sspec
+        order, n_order, resume = None, n, 0
+        while True:
+            traj = L.Traj(*[L.ptr(t) for t in (boards, actions, rewards, flags, probs, lengths, totals, max_e, final)])
+            L.check(self._lib.g2048_sized_rollout(self.size, L.ptr(packed), len(hidden), harr, act, ctypes.byref(cfg),
+                                                  int(use_greedy), *[L.ptr(t) for t in streams], L.ptr(queue),
+                                                  L.ptr(order), n_order, resume, ctypes.byref(sus), n, cap,
+                                                  ctypes.byref(traj), cap * n, int(self.sized_rollout_max_workgroups),
+                                                  self._stream))
+            k = int(sus_count.item())          # one host sync per launch
+            if k == 0:
+                break
+            order, n_order, resume = sus_list[:k].clone(), k, 1
+            queue.zero_()
+            sus_count.zero_()
+            grow = cap if ms is None else max(min(cap, int(ms) - cap), 1)   # never past max_steps rows
+            # as _rollout_deep: an episode that never ends must not run the device out of memory
+            row_bytes = n * (8 * W + 1 + 8 + 1 + (16 if probs is not None else 0))
+            free_b = 1 << 62
+            if dev.type == "cuda":
+                free_b = (torch.cuda.mem_get_info(dev)[0] + torch.cuda.memory_reserved(dev) -
+                          torch.cuda.memory_allocated(dev))
+            if cap + grow > self.sized_rollout_max_rows or (cap + grow) * row_bytes > free_b + cap * row_bytes // 2:
+                hint = "set max_steps" + ("" if self.env_config.use_action_mask else " or use_action_mask=True")
+                raise RuntimeError(
+                    f"rollout_batch (max_steps=None): {k} episode(s) still running after {cap} steps; growing the "
+                    f"[T, n] trajectory buffer to {cap + grow} rows needs {(cap + grow) * row_bytes / 2**30:.1f} GiB "
+                    f"(free: {free_b / 2**30:.1f} GiB, row limit {self.sized_rollout_max_rows}) -- {hint}")
+            boards = torch.cat([boards, torch.empty(W, grow, n, dtype=torch.int64, device=dev)], dim=1)
+            actions = torch.cat([actions, torch.zeros(grow, n, dtype=torch.uint8, device=dev)])
+            rewards = torch.cat([rewards, torch.zeros(grow, n, dtype=torch.float64, device=dev)])
+            flags = torch.cat([flags, torch.full((grow, n), L.F_INACTIVE, dtype=torch.uint8, device=dev)])
+            if probs is not None:
+                probs = torch.cat([probs, torch.zeros(grow, n, 4, dtype=torch.float32, device=dev)])
+            cap += grow
+        T = int(lengths.max().item()) if n else 0
+        return TrajectoryBatch(boards=boards[:, :T], actions=actions[:T], rewards=rewards[:T], flags=flags[:T],
                                lengths=lengths, total_reward=totals,
                                max_tile=torch.ones(n, dtype=torch.int64, device=dev) << max_e.to(torch.int64),
                                final_boards=final, probs=probs[:T] if probs is not None else None)
