@@ -117,6 +117,67 @@ int g2048_sized_rollout(int size, const float* packed, int n_hidden, const int32
                         int64_t n, int64_t cap, const g2048_traj* traj, int64_t board_stride, int max_workgroups,
                         void* stream);
 
+/* The fused gradient for size N (g2048_sized_grad.hip; additive, ABI still 17): g2048_deep_grad and g2048_onehot_dw1
+ * for these boards -- update_batch's actor or critic gradient of n samples in one launch, straight from the board
+ * planes, on a net packed by g2048_sized_pack (forward) and g2048_deep_grad_pack (the dense layers' backward
+ * fragments: layers l >= 1 only, so they do not depend on the size).
+ *
+ * Coverage (g2048_sized_grad_slab >= 0): size 2..8; raw / log2 / one-hot obs; ReLU / Sigmoid; 1..4 hidden layers of
+ * 1..256 units whose dense 32 x 32 weight-gradient tiles, sum over l >= 1 of ceil(H_{l-1} / 32) ceil(H_l / 32), number
+ * at most 40 on one-hot obs (e.g. [256, 128, 64]) and at most 32 on raw / log2 (e.g. [256, 128]), and whose LDS bill
+ * fits 160 KiB.  One launch only: there is no multi-launch form, and every other net returns -1 / G2048_EINVAL.
+ *
+ * Partial slab (floats; H_l p = H_l rounded up to 32; g2048_deep_grad's with layer 0 sized to the board):
+ *   dW_0  [rows0][H_0 p]  raw / log2 only: rows0 = 32 ceil(N*N / 32) feature rows (32 for N <= 5, 64 for N >= 6), the
+ *                         rows >= N*N zero; one-hot: absent (g2048_sized_onehot_dw1 forms it from d0_out)
+ *   db_0  [H_0 p]
+ *   dW_l  [H_{l-1} p][H_l p], db_l [H_l p]    for l = 1 .. L-1
+ *   dW_out [H_{L-1} p][4], db_out [4]
+ * g2048_sized_grad_layout returns these offsets.  Raw / log2 dW_0 is formed inside the kernel at every size (no
+ * d0_out fall-back was needed: 0 spilled registers with both feature tiles held). */
+/* Floats per partial slab, or -1 when the net is not covered.  Host arithmetic only. */
+int g2048_sized_grad_slab(int size, int obs_mode, int n_hidden, const int32_t* hidden);
+/* The workgroup count (nparts) that fills the device: one 8-wave workgroup per CU; -1 when not covered.  Unlike the
+ * slab and layout queries this one touches the HIP runtime for a covered net (hipGetDevice / hipDeviceGetAttribute on
+ * the current device's CU count) and answers 256 where no device can be asked. */
+int g2048_sized_grad_parts(int size, int obs_mode, int n_hidden, const int32_t* hidden);
+/* The slab layout: w_off[l] / b_off[l] (n_hidden + 1 entries each, NULL ok) = float offsets of dW_l / db_l, entry
+ * n_hidden the output layer's; *dw0_rows = rows0 (0 on one-hot obs), *dw0_ld = H_0 p (NULL ok).  Returns the slab size
+ * or -1 when not covered.  Host arithmetic only. */
+int g2048_sized_grad_layout(int size, int obs_mode, int n_hidden, const int32_t* hidden, int32_t* w_off,
+                            int32_t* b_off, int32_t* dw0_rows, int32_t* dw0_ld);
+/* g2048_deep_grad for size N on plane-major boards (word w of sample j at boards[w * plane_stride + j]); the contract
+ * is g2048_deep_grad's: critic = 0 the policy-gradient branch (actions, coef = advantage x step weight, the mask of
+ * each board when use_mask), critic = 1 the value loss (loss 0 = MSE, 1 = Huber with huber_delta; coef = step weight;
+ * target = r + gamma V(s') m; delta_out = target - V and value_out = V, [n], NULL ok); every one of the nparts
+ * workgroups writes a complete slab into partials [nparts][slab], zeros when it gets no group of 32 samples, to be
+ * summed by g2048_fold_partials.  There is no TD-row argument.  d0_out [n][H_0 p] is required on one-hot obs (layer
+ * 0's deltas for g2048_sized_onehot_dw1) and ignored otherwise.
+ * hidden_out (NULL ok; production calls pass NULL): n_hidden pointers, entry l (NULL ok) receives hidden layer l's
+ * activations [n][H_l p] exactly as the kernel's forward computed them (stored after the forward, before the deltas
+ * overwrite them) -- the kernel's own ReLU pattern, for tests and diagnostics.
+ * G2048_EINVAL before any HIP call for a size outside 2..8, plane_stride < n, n < 0 or n > 2^30, a net
+ * g2048_sized_grad_slab does not cover, a bad activation / obs mode / loss, nparts outside 1..65535 or a NULL
+ * required buffer (packed, partials; grad_packed when n_hidden > 1; with n > 0: boards, coef, actions (actor), target
+ * (critic), d0_out (one-hot)).  n == 0 returns G2048_OK without a launch: partials is left untouched. */
+int g2048_sized_grad(int size, const float* packed, const float* grad_packed, int n_hidden, const int32_t* hidden,
+                     int activation, int obs_mode, float obs_scale, int use_mask, const uint64_t* boards,
+                     int64_t plane_stride, const uint8_t* actions, const float* coef, int critic, int loss,
+                     float huber_delta, const float* target, float* delta_out, float* value_out, float* d0_out,
+                     float* const* hidden_out, int64_t n, float* partials, int64_t nparts, void* stream);
+/* Floats per partial slab of g2048_sized_onehot_dw1: (17 N*N + 1) h1 (17 N*N rows of dW_0, then db_0), or -1 for a
+ * size outside 2..8 or h1 outside 1..256. */
+int g2048_sized_onehot_dw1_slab(int size, int h1);
+/* g2048_onehot_dw1 for size N: dW_0 / db_0 of a one-hot first layer from the board planes and the layer's deltas d1
+ * [m][ld] (units < h1 <= ld).  Row 17 k + e of a slab is cell k = r*N + c, exponent e (g2048_sized_pack's row order;
+ * rows 17 k + 16 are zero); workgroups (i, w) take samples [i per, (i + 1) per) and board word w, nparts = ceil(m /
+ * per) slabs, summed by g2048_fold_partials.  Same arithmetic as g2048_onehot_dw1 (the exact one-hot operand against
+ * each delta's three exact bf16 planes, fp32 accumulation in a fixed order: deterministic, no atomics).
+ * G2048_EINVAL for a size outside 2..8, plane_stride < m, m > 2^30 and by g2048_onehot_dw1's rules; m == 0 returns
+ * G2048_OK without a launch. */
+int g2048_sized_onehot_dw1(int size, const uint64_t* boards, int64_t plane_stride, const float* d1, int h1, int64_t m,
+                           int64_t ld, int64_t per, float* partials, int64_t nparts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

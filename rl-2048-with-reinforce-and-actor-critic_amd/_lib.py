@@ -21,7 +21,8 @@ SRC = os.path.join(PKG_DIR, "csrc", "g2048.hip")
 SOURCES = [SRC, os.path.join(PKG_DIR, "csrc", "g2048_policy.hip"), os.path.join(PKG_DIR, "csrc", "g2048_dw2.hip"),
            os.path.join(PKG_DIR, "csrc", "g2048_deep.hip"), os.path.join(PKG_DIR, "csrc", "g2048_sized.hip"),
            os.path.join(PKG_DIR, "csrc", "g2048_sized_policy.hip"),
-           os.path.join(PKG_DIR, "csrc", "g2048_sized_rollout.hip")]
+           os.path.join(PKG_DIR, "csrc", "g2048_sized_rollout.hip"),
+           os.path.join(PKG_DIR, "csrc", "g2048_sized_grad.hip")]
 INCLUDE = os.path.join(REPO_ROOT, "include")
 ABI_VERSION = 17
 DEEP_MAX_HIDDEN = 4
@@ -226,9 +227,14 @@ def _declare(L):
                                      vp, vp, vp, i64, vp]
     L.g2048_sized_rollout.argtypes = [i32, vp, i32, vp, i32, P(EnvCfg), i32, vp, vp, vp, vp, vp, vp, vp, vp, i64, i32,
                                       P(Suspend), i64, i64, P(Traj), i64, i32, vp]
-    for name in ("g2048_sized_words", "g2048_sized_reset", "g2048_sized_step", "g2048_sized_obs", "g2048_sized_move",
-                 "g2048_sized_symmetries", "g2048_sized_policy_packed_size", "g2048_sized_pack", "g2048_sized_policy",
-                 "g2048_sized_rollout"):
+    L.g2048_sized_grad_slab.argtypes = [i32, i32, i32, vp]
+    L.g2048_sized_grad_parts.argtypes = [i32, i32, i32, vp]
+    L.g2048_sized_grad_layout.argtypes = [i32, i32, i32, vp, vp, vp, vp, vp]
+    L.g2048_sized_grad.argtypes = [i32, vp, vp, i32, vp, i32, i32, f, i32, vp, i64, vp, vp, i32, i32, f, vp, vp, vp, vp,
+                                   vp, i64, vp, i64, vp]
+    L.g2048_sized_onehot_dw1_slab.argtypes = [i32, i32]
+    L.g2048_sized_onehot_dw1.argtypes = [i32, vp, i64, vp, i32, i64, i64, i64, vp, i64, vp]
+    for name in SIZED_SYMBOLS:
         getattr(L, name).restype = ctypes.c_int
     for name in ("g2048_init", "g2048_seed_pcg64", "g2048_reset", "g2048_step", "g2048_obs", "g2048_move",
                  "g2048_sample", "g2048_returns", "g2048_symmetries", "g2048_policy_pack", "g2048_policy",
@@ -252,7 +258,8 @@ EXPORTED_SYMBOLS = ("g2048_abi_version", "g2048_last_error", "g2048_init", "g204
 # include/g2048_sized.h (included by g2048.h): board sizes 2..8
 SIZED_SYMBOLS = ("g2048_sized_words", "g2048_sized_reset", "g2048_sized_step", "g2048_sized_obs", "g2048_sized_move",
                  "g2048_sized_symmetries", "g2048_sized_policy_packed_size", "g2048_sized_pack", "g2048_sized_policy",
-                 "g2048_sized_rollout")
+                 "g2048_sized_rollout", "g2048_sized_grad_slab", "g2048_sized_grad_parts", "g2048_sized_grad_layout",
+                 "g2048_sized_grad", "g2048_sized_onehot_dw1_slab", "g2048_sized_onehot_dw1")
 
 
 def lib():

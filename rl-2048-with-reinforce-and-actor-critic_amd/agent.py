@@ -745,6 +745,128 @@ class ReinforceAgent:
         gW[nh] += acc[pw[nh]:pw[nh] + Hp[-1] * 4].view(Hp[-1], 4)[:hidden[-1], :out_dim]
         gb[nh] += acc[pb[nh]:pb[nh] + 4][:out_dim]
 
+    # Board sizes other than 4: update_batch's actor / critic gradients through g2048_sized_grad (one fused launch per
+    # chunk, straight from the board planes) when the net fits it (_sized_grad_spec).  Off by default: the general
+    # path (g2048_sized_obs + hipBLASLt forward + torch backward) stays the product path
+    use_fused_sized_grad = False
+
+    def _sized_grad_spec(self, params, out_dim: int):
+        """_sized_spec when the switch is on and g2048_sized_grad covers the net in its one launch (at most 40 dense
+        32 x 32 weight-gradient tiles on one-hot obs, 32 on raw / log2), else None."""
+        if not self.use_fused_sized_grad:
+            return None
+        s = self._sized_spec(params, out_dim)
+        if s is None or int(self._lib.g2048_sized_grad_slab(self.size, s[0], len(s[1]), s[3])) < 0:
+            return None
+        return s
+
+    @staticmethod
+    def _sized_slab_layout(size: int, hidden, onehot: bool):
+        """(pw, pb, rows0, slab): float offsets of dW_l / db_l in g2048_sized_grad's partial slab, the row count of
+        its dW_0 (0 on one-hot obs) and its size (include/g2048_sized.h; g2048_sized_grad_layout is the C side)."""
+        Hp = [_round32(h) for h in hidden]
+        rows0 = 0 if onehot else _round32(size * size)
+        pw, pb, off = [], [], 0
+        for l in range(len(hidden)):
+            pw.append(off)
+            off += rows0 * Hp[0] if l == 0 else Hp[l - 1] * Hp[l]
+            pb.append(off)
+            off += Hp[l]
+        pw.append(off)
+        off += Hp[-1] * 4
+        pb.append(off)
+        return pw, pb, rows0, off + 4
+
+    def _sized_forward(self, params, sspec, slot: str, boards: torch.Tensor, out_dim: int) -> torch.Tensor:
+        """forward_logits of [W, m] board planes through g2048_sized_policy (forward only): [m, 4] (a value head in
+        column 0)."""
+        m = boards.shape[-1]
+        out = torch.empty(m, 4, dtype=torch.float32, device=self.device)
+        if m == 0:
+            return out
+        packed = self._pack_sized(params, sspec, slot, out_dim)
+        obs_code, hidden, act, harr = sspec
+        L.check(self._lib.g2048_sized_policy(self.size, L.ptr(packed), len(hidden), harr, act,
+                                             L.ptr(boards.contiguous()), m, None, None, obs_code,
+                                             float(self.env_config.obs_log2_scale), 0, 1, L.RNG_PCG64, None, None,
+                                             None, 0, None, None, L.ptr(out), None, m, self._stream))
+        return out
+
+    def _sized_onehot_dw1_into(self, boards: torch.Tensor, d1: torch.Tensor, acc: torch.Tensor, h1: int) -> None:
+        """_onehot_dw1_into for [W, m] board planes: acc (fp64 [(17 N*N + 1) h1]) += g2048_sized_onehot_dw1's partial
+        slabs of the deltas d1 [m, ld], folded in fp64."""
+        m, ld = d1.shape
+        if m == 0:
+            return
+        cus = int(self._lib.g2048_actor_grad_waves()) // 4
+        per = max(512, -(-m // (16 * cus)) * 16)         # about one workgroup per CU and word, whole 16-sample steps
+        nparts = -(-m // per)
+        part = torch.empty(nparts, int(self._lib.g2048_sized_onehot_dw1_slab(self.size, h1)), dtype=torch.float32,
+                           device=self.device)
+        L.check(self._lib.g2048_sized_onehot_dw1(self.size, L.ptr(boards), m, L.ptr(d1), h1, m, ld, per, L.ptr(part),
+                                                 nparts, self._stream))
+        self._fold(part, acc)
+
+    def _sized_grad_fused(self, params, slot: str, sspec, steps: "_Steps", K: int, gW: list[torch.Tensor],
+                          gb: list[torch.Tensor], out_dim: int, adv=None, step_w=None, deltas=None) -> None:
+        """_deep_grad_fused for board sizes other than 4: update_batch's actor (adv given) or critic (deltas given)
+        branch through g2048_sized_grad on the [W, m] board planes, chunked; the critic's V(s') by g2048_sized_policy's
+        forward; one-hot first layers by g2048_sized_onehot_dw1 on the kernel's layer-0 deltas.  Accumulates into
+        gW / gb like mlp_backward_."""
+        c = self.agent_config
+        obs_code, hidden, act, harr = sspec
+        nh = len(hidden)
+        onehot = obs_code == L.OBS_ONEHOT
+        critic = deltas is not None
+        packed = self._pack_sized(params, sspec, slot, out_dim)
+        bpacked = self._pack_deep_grad(params, sspec, slot)
+        nparts = int(self._lib.g2048_sized_grad_parts(self.size, obs_code, nh, harr))   # fills the chip
+        pw, pb, rows0, slab = self._sized_slab_layout(self.size, hidden, onehot)
+        assert slab == int(self._lib.g2048_sized_grad_slab(self.size, obs_code, nh, harr))
+        part = torch.empty(nparts, slab, dtype=torch.float32, device=self.device)
+        acc = torch.zeros(slab, dtype=torch.float64, device=self.device)
+        h0, H0p = hidden[0], _round32(hidden[0])
+        rows1 = 17 * self.size * self.size
+        acc1 = torch.zeros((rows1 + 1) * h0, dtype=torch.float64, device=self.device) if onehot else None
+        use_mask = int(bool(self.env_config.use_action_mask))
+        loss = {"mse": 0, "huber": 1}[c.critic_loss_type] if critic else 0
+        scale = float(self.env_config.obs_log2_scale)
+        for k in range(K):
+            for s0 in range(0, steps.N, self.grad_chunk_steps):
+                m = min(self.grad_chunk_steps, steps.N - s0)
+                sel = torch.arange(s0, s0 + m, device=self.device)
+                b = steps.boards_at(sel, k).contiguous()          # [W, m] planes
+                acts = tgt = None
+                if critic:
+                    hn = steps.has_next[sel]
+                    vn = self._sized_forward(params, sspec, slot, steps.boards_at(sel, k, nxt=True), 1)[:, 0]
+                    tgt = (steps.rewards[sel] + (float(c.gamma) * vn) * hn.to(torch.float32)).contiguous()
+                    coef = step_w[sel].contiguous()
+                else:
+                    acts = steps.actions_k(sel, k).to(torch.uint8).contiguous()
+                    coef = (adv[k, sel] * step_w[sel]).contiguous()
+                d0 = torch.empty(m, H0p, dtype=torch.float32, device=self.device) if onehot else None
+                L.check(self._lib.g2048_sized_grad(self.size, L.ptr(packed), L.ptr(bpacked), nh, harr, act, obs_code,
+                                                   scale, use_mask, L.ptr(b), m, L.ptr(acts), L.ptr(coef), int(critic),
+                                                   loss, float(c.huber_delta), L.ptr(tgt),
+                                                   L.ptr(deltas[k, s0:s0 + m]) if critic else None, None, L.ptr(d0),
+                                                   None, m, L.ptr(part), nparts, self._stream))
+                self._fold(part, acc)
+                if onehot:
+                    self._sized_onehot_dw1_into(b, d0, acc1, h0)
+        Hp = [_round32(h) for h in hidden]
+        acc = acc.to(torch.float32)
+        if onehot:
+            gW[0] += acc1[:rows1 * h0].view(rows1, h0).to(torch.float32)
+        else:
+            gW[0] += acc[pw[0]:pw[0] + rows0 * Hp[0]].view(rows0, Hp[0])[:self.size * self.size, :h0]
+        gb[0] += acc[pb[0]:pb[0] + Hp[0]][:h0]
+        for l in range(1, nh):
+            gW[l] += acc[pw[l]:pw[l] + Hp[l - 1] * Hp[l]].view(Hp[l - 1], Hp[l])[:hidden[l - 1], :hidden[l]]
+            gb[l] += acc[pb[l]:pb[l] + Hp[l]][:hidden[l]]
+        gW[nh] += acc[pw[nh]:pw[nh] + Hp[-1] * 4].view(Hp[-1], 4)[:hidden[-1], :out_dim]
+        gb[nh] += acc[pb[nh]:pb[nh] + 4][:out_dim]
+
     def _td_rows(self, steps: "_Steps", hn_f: torch.Tensor, s0: int, cnt: int, v_next: torch.Tensor,
                  v_out: torch.Tensor):
         """g2048_td_rows of time row [s0, s0 + cnt): the kernel forms r + (gamma V(s')) m from the later row's
@@ -1813,6 +1935,15 @@ class ReinforceAgent:
                         self._deep_grad_fused(self.critic_params, "critic", cdg, steps, K, critic_g[:ncW],
                                               critic_g[ncW:], 1, step_w=step_w, deltas=deltas)
                 cspec = cdg      # handled: skip the torch loop below
+            csg = (self._sized_grad_spec(self.critic_params, 1) if cspec is None and steps.boards is not None and
+                   c.critic_loss_type in ("mse", "huber") else None)
+            if csg is not None:
+                self._paths["critic_grad"] = "g2048_sized_grad" + (" + g2048_sized_onehot_dw1" if
+                                                                  csg[0] == L.OBS_ONEHOT else "")
+                with torch.no_grad():
+                    self._sized_grad_fused(self.critic_params, "critic", csg, steps, K, critic_g[:ncW],
+                                           critic_g[ncW:], 1, step_w=step_w, deltas=deltas)
+                cspec = csg      # handled: skip the torch loop below
             cdspec = self._deep_spec(self.critic_params, 1) if cspec is None and steps.boards is not None else None
             oh1 = self._onehot_first_layer(steps) and cspec is None
             acc1c = torch.zeros(273 * int(self.critic_params["W"][0].shape[1]), dtype=torch.float64,
@@ -1867,8 +1998,16 @@ class ReinforceAgent:
         gspec = self._fused_grad_spec() if steps.boards is not None else None
         self._paths["actor_grad"] = "g2048_actor_grad + g2048_dw2" if gspec is not None else "hipBLASLt backprop"
         adg = self._deep_grad_spec(self.params, 4) if gspec is None and steps.boards is not None else None
+        asg = (self._sized_grad_spec(self.params, 4) if gspec is None and adg is None and steps.boards is not None
+               else None)
         with torch.no_grad():
-            if gspec is not None:
+            if asg is not None:
+                self._paths["actor_grad"] = "g2048_sized_grad" + (" + g2048_sized_onehot_dw1" if
+                                                                 asg[0] == L.OBS_ONEHOT else "")
+                self._sized_grad_fused(self.params, "actor", asg, steps, K, actor_g[:nW], actor_g[nW:], 4, adv=adv,
+                                       step_w=step_w)
+                gspec = asg      # handled: skip the torch loop below
+            elif gspec is not None:
                 self._actor_grad_fused(steps, adv, step_w, K, actor_g[:nW], actor_g[nW:], gspec)
             elif adg is not None:
                 self._paths["actor_grad"] = "g2048_deep_grad" + (" + g2048_onehot_dw1" if adg[0] == L.OBS_ONEHOT
