@@ -433,6 +433,9 @@ int g2048_onehot_dw1(const uint64_t* boards, const float* d1, int h1, int64_t m,
 }
 #endif
 
+/* score-only rollouts (no trajectory rows): additive entry points of ABI 17, part of this interface */
+#include "g2048_eval.h"
+
 /* board sizes 2..8: the g2048_sized_* entry points (ABI 17), part of this interface */
 #include "g2048_sized.h"
 

@@ -116,6 +116,19 @@ int g2048_sized_rollout(int size, const float* packed, int n_hidden, const int32
                         uint32_t* queue, const int32_t* order, int64_t n_order, int resume, const g2048_suspend* sus,
                         int64_t n, int64_t cap, const g2048_traj* traj, int64_t board_stride, int max_workgroups,
                         void* stream);
+/* g2048_deep_eval for size N (g2048_sized_eval.hip; additive, ABI still 17): g2048_sized_rollout's kernels with the
+ * trajectory row stores compiled out, so the same episodes and memory that does not depend on their lengths.
+ * step_limit (1 .. 2^31 - 1) is the absolute step count at which an episode still running is suspended in this call
+ * (g2048_eval.h); there is no board_stride and no n * step_limit limit.  out->final_board and sus->board are [W, n]
+ * planes of stride n.  Every other argument and rule, max_workgroups and the grid included, is g2048_sized_rollout's;
+ * G2048_EINVAL before any HIP call for whatever that rejects that still applies, for a NULL out or field of out and
+ * for step_limit < 1; n_order == 0 returns G2048_OK without a launch.
+ * g2048_eval_out is declared in g2048_eval.h, which g2048.h includes before this file. */
+int g2048_sized_eval(int size, const float* packed, int n_hidden, const int32_t* hidden, int activation,
+                     const g2048_env_cfg* cfg, int greedy, uint64_t* env_state, const uint64_t* env_inc,
+                     uint64_t* env_buf, uint64_t* pol_state, const uint64_t* pol_inc, uint64_t* pol_buf,
+                     uint32_t* queue, const int32_t* order, int64_t n_order, int resume, const g2048_suspend* sus,
+                     int64_t n, int64_t step_limit, const g2048_eval_out* out, int max_workgroups, void* stream);
 
 /* The fused gradient for size N (g2048_sized_grad.hip; additive, ABI still 17): g2048_deep_grad and g2048_onehot_dw1
  * for these boards -- update_batch's actor or critic gradient of n samples in one launch, straight from the board

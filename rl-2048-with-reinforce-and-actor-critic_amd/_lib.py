@@ -22,7 +22,11 @@ SOURCES = [SRC, os.path.join(PKG_DIR, "csrc", "g2048_policy.hip"), os.path.join(
            os.path.join(PKG_DIR, "csrc", "g2048_deep.hip"), os.path.join(PKG_DIR, "csrc", "g2048_sized.hip"),
            os.path.join(PKG_DIR, "csrc", "g2048_sized_policy.hip"),
            os.path.join(PKG_DIR, "csrc", "g2048_sized_rollout.hip"),
-           os.path.join(PKG_DIR, "csrc", "g2048_sized_grad.hip")]
+           os.path.join(PKG_DIR, "csrc", "g2048_sized_grad.hip"),
+           # the score-only (no trajectory row) instantiations of the persistent rollout kernels, in units of their
+           # own so that they compile beside the trajectory forms
+           os.path.join(PKG_DIR, "csrc", "g2048_rollout_eval.hip"),
+           os.path.join(PKG_DIR, "csrc", "g2048_sized_eval.hip")]
 INCLUDE = os.path.join(REPO_ROOT, "include")
 ABI_VERSION = 17
 DEEP_MAX_HIDDEN = 4
@@ -69,7 +73,8 @@ def _object_for(src: str, flags: list[str]) -> str:
     h = hashlib.sha256(" ".join(flags).encode())
     h.update(_compiler_id().encode())
     hdrs = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".inc")))
-    for f in [src] + hdrs + [os.path.join(INCLUDE, "g2048.h"), os.path.join(INCLUDE, "g2048_sized.h")]:
+    for f in [src] + hdrs + [os.path.join(INCLUDE, "g2048.h"), os.path.join(INCLUDE, "g2048_sized.h"),
+                                os.path.join(INCLUDE, "g2048_eval.h")]:
         with open(f, "rb") as fh:
             h.update(fh.read())
     return os.path.join(BUILD_DIR, f"{os.path.splitext(os.path.basename(src))[0]}-{h.hexdigest()[:16]}.o")
@@ -153,6 +158,11 @@ class Suspend(ctypes.Structure):
     _fields_ = [(name, ctypes.c_void_p) for name in ("board", "meta", "total", "list", "count")]
 
 
+class EvalOut(ctypes.Structure):
+    """g2048_eval_out: what a score-only rollout keeps of an episode (the per-episode fields of Traj)."""
+    _fields_ = [(name, ctypes.c_void_p) for name in ("lengths", "totals", "max_tile", "final_board")]
+
+
 _lib = None
 _lock = threading.RLock()
 _inited_devices: set[int] = set()
@@ -234,7 +244,12 @@ def _declare(L):
                                    vp, i64, vp, i64, vp]
     L.g2048_sized_onehot_dw1_slab.argtypes = [i32, i32]
     L.g2048_sized_onehot_dw1.argtypes = [i32, vp, i64, vp, i32, i64, i64, i64, vp, i64, vp]
-    for name in SIZED_SYMBOLS:
+    L.g2048_rollout_eval.argtypes = [vp, i32, i32, i32, P(EnvCfg), i32, vp, vp, vp, vp, vp, vp, vp, i64, P(EvalOut), vp]
+    L.g2048_deep_eval.argtypes = [vp, i32, vp, i32, P(EnvCfg), i32, vp, vp, vp, vp, vp, vp, vp, vp, i64, i32,
+                                  P(Suspend), i64, i64, P(EvalOut), vp]
+    L.g2048_sized_eval.argtypes = [i32, vp, i32, vp, i32, P(EnvCfg), i32, vp, vp, vp, vp, vp, vp, vp, vp, i64, i32,
+                                   P(Suspend), i64, i64, P(EvalOut), i32, vp]
+    for name in SIZED_SYMBOLS + EVAL_SYMBOLS:
         getattr(L, name).restype = ctypes.c_int
     for name in ("g2048_init", "g2048_seed_pcg64", "g2048_reset", "g2048_step", "g2048_obs", "g2048_move",
                  "g2048_sample", "g2048_returns", "g2048_symmetries", "g2048_policy_pack", "g2048_policy",
@@ -258,8 +273,13 @@ EXPORTED_SYMBOLS = ("g2048_abi_version", "g2048_last_error", "g2048_init", "g204
 # include/g2048_sized.h (included by g2048.h): board sizes 2..8
 SIZED_SYMBOLS = ("g2048_sized_words", "g2048_sized_reset", "g2048_sized_step", "g2048_sized_obs", "g2048_sized_move",
                  "g2048_sized_symmetries", "g2048_sized_policy_packed_size", "g2048_sized_pack", "g2048_sized_policy",
-                 "g2048_sized_rollout", "g2048_sized_grad_slab", "g2048_sized_grad_parts", "g2048_sized_grad_layout",
-                 "g2048_sized_grad", "g2048_sized_onehot_dw1_slab", "g2048_sized_onehot_dw1")
+                 "g2048_sized_rollout", "g2048_sized_eval", "g2048_sized_grad_slab", "g2048_sized_grad_parts",
+                 "g2048_sized_grad_layout", "g2048_sized_grad", "g2048_sized_onehot_dw1_slab",
+                 "g2048_sized_onehot_dw1")
+
+# include/g2048_eval.h (included by g2048.h): score-only rollouts of the 4 x 4 families (g2048_sized_eval, their
+# counterpart for sizes 2..8, is declared with the sized entry points)
+EVAL_SYMBOLS = ("g2048_rollout_eval", "g2048_deep_eval")
 
 
 def lib():

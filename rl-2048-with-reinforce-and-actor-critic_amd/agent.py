@@ -90,6 +90,21 @@ class TrajectoryBatch:
         return int(self.actions.shape[0])
 
 
+@dataclass
+class EvalBatch:
+    """What an evaluation reads of one batch of episodes (ReinforceAgent.evaluate_batch): the per-episode fields of
+    TrajectoryBatch, same dtypes, shapes and meaning, without the time-major rows."""
+    lengths: torch.Tensor      # [n] int32
+    total_reward: torch.Tensor  # [n] float64
+    max_tile: torch.Tensor     # [n] int64
+    final_boards: torch.Tensor  # [n] int64 (size 4); [W, n] for any other size
+    shard_sizes: tuple[int, ...] | None = None   # as TrajectoryBatch.shard_sizes
+
+    @property
+    def n(self) -> int:
+        return int(self.lengths.numel())
+
+
 def _seed_seq(seeds):
     """A batch of episode seeds as a tensor / numpy array (kept: the fast conversion path) or a list."""
     return seeds if isinstance(seeds, (torch.Tensor, np.ndarray)) else list(seeds)
@@ -1690,6 +1705,117 @@ class ReinforceAgent:
                                lengths=lengths, total_reward=totals,
                                max_tile=torch.ones(n, dtype=torch.int64, device=dev) << max_e.to(torch.int64),
                                final_boards=final, probs=probs[:T] if probs is not None else None)
+
+    # Score-only evaluation (evaluate_batch): the steps a persistent launch of g2048_deep_eval / g2048_sized_eval may
+    # add to an episode before it suspends it (so every launch is bounded), and the step count past which a still
+    # running episode is refused (an episode that never ends -- max_steps None with invalid actions allowed, where the
+    # reference itself loops forever -- raises instead of being relaunched for ever).  Class attributes, so that they
+    # can be set for agents somebody else constructs.
+    eval_step_budget = 4096
+    eval_max_steps = 1 << 20
+
+    def evaluate_batch(self, env_seeds, policy_seeds, use_greedy: bool = True, rng: str = "pcg64") -> EvalBatch:
+        """The episodes rollout_batch plays for these seeds under the same agent settings, keeping only what an
+        evaluation reads of them (lengths, total_reward, max_tile, final_boards): no trajectory rows, so memory is O(n)
+        whatever the episodes' lengths.  The family is chosen by rollout_batch's own tests in its order; what no
+        persistent kernel covers goes through rollout_batch itself.  last_paths()["eval"] names what ran."""
+        n = len(env_seeds)
+        if len(policy_seeds) != n:
+            raise ValueError("env_seeds and policy_seeds must have the same length")
+        spec = self._fused_policy_spec()
+        if spec is not None and rng == "pcg64" and self.env_config.max_steps is not None and self.use_fused_rollout:
+            self._paths["eval"] = "g2048_rollout_eval (one persistent launch, no trajectory rows)"
+            return self._evaluate_persistent(env_seeds, policy_seeds, "fused", spec, use_greedy)
+        dspec = self._deep_spec() if self.use_fused_policy else None
+        if dspec is not None and rng == "pcg64" and self.use_fused_rollout:
+            self._paths["eval"] = "g2048_deep_eval (persistent launches, no trajectory rows, suspended episodes resumed)"
+            return self._evaluate_persistent(env_seeds, policy_seeds, "deep", dspec, use_greedy)
+        if self._sized and self.use_fused_sized_rollout and rng == "pcg64":
+            rspec = self._sized_spec()
+            if rspec is not None:
+                self._paths["eval"] = ("g2048_sized_eval (persistent launches, no trajectory rows, suspended episodes "
+                                       "resumed)")
+                return self._evaluate_persistent(env_seeds, policy_seeds, "sized", rspec, use_greedy)
+        b = self.rollout_batch(env_seeds, policy_seeds, use_greedy=use_greedy, rng=rng)
+        self._paths["eval"] = "rollout_batch (trajectory rows materialised): " + self._paths["rollout"]
+        return EvalBatch(lengths=b.lengths, total_reward=b.total_reward, max_tile=b.max_tile,
+                         final_boards=b.final_boards)
+
+    def _evaluate_persistent(self, env_seeds, policy_seeds, family: str, spec, use_greedy: bool) -> EvalBatch:
+        """evaluate_batch through the score-only form of a persistent rollout kernel (family "fused": g2048_rollout_eval,
+        one launch bounded by max_steps; "deep" / "sized": g2048_deep_eval / g2048_sized_eval, relaunching the episodes
+        the kernel suspended every eval_step_budget steps).  Allocates per episode the two streams and their seeds, the
+        four outputs and the suspend state; nothing grows between launches."""
+        from .config import env_cfg_struct
+        from .vec_env import _as_u64_seeds
+
+        n = len(env_seeds)
+        dev = self.device
+        W = int(self._lib.g2048_sized_words(self.size)) if family == "sized" else 1
+        planes = (lambda: torch.empty(W, n, dtype=torch.int64, device=dev)) if family == "sized" else \
+                 (lambda: torch.empty(n, dtype=torch.int64, device=dev))
+        es = _as_u64_seeds(_seed_seq(env_seeds), n, 0, dev)
+        ps = _as_u64_seeds(_seed_seq(policy_seeds), n, 0, dev)
+        streams = []
+        for seeds in (es, ps):
+            st = torch.empty(2 * n, dtype=torch.int64, device=dev)
+            inc = torch.empty(2 * n, dtype=torch.int64, device=dev)
+            buf = torch.empty(n, dtype=torch.int64, device=dev)
+            L.check(self._lib.g2048_seed_pcg64(L.ptr(seeds), L.ptr(st), L.ptr(inc), L.ptr(buf), n, self._stream))
+            streams += [st, inc, buf]
+        lengths = torch.empty(n, dtype=torch.int32, device=dev)
+        totals = torch.empty(n, dtype=torch.float64, device=dev)
+        max_e = torch.empty(n, dtype=torch.uint8, device=dev)
+        final = planes()
+        out = L.EvalOut(*[L.ptr(t) for t in (lengths, totals, max_e, final)])
+        queue = torch.zeros(1, dtype=torch.int32, device=dev)
+        cfg = env_cfg_struct(self.env_config)
+        if family == "fused":
+            packed = self._packed_policy(spec)
+            L.check(self._lib.g2048_rollout_eval(L.ptr(packed), spec[0], spec[1], spec[2], ctypes.byref(cfg),
+                                                 int(use_greedy), *[L.ptr(t) for t in streams], L.ptr(queue), n,
+                                                 ctypes.byref(out), self._stream))
+        else:
+            sus_board = planes()
+            sus_meta = torch.empty(3 * n, dtype=torch.int32, device=dev)
+            sus_total = torch.empty(n, dtype=torch.float64, device=dev)
+            # two episode lists: the one a launch reads as its order and the one it fills with what it suspends
+            lists = [torch.empty(max(n, 1), dtype=torch.int32, device=dev) for _ in range(2)]
+            sus_count = torch.zeros(1, dtype=torch.int32, device=dev)
+            _, hidden, act, harr = spec
+            if family == "deep":
+                packed = self._pack_deep(self.params, spec, "actor", 4)
+            else:
+                packed = self._pack_sized(self.params, spec, "actor", 4)
+            budget = max(int(self.eval_step_budget), 1)
+            most = max(int(self.eval_max_steps), 1)
+            limit = min(budget, most)                   # no launch plays an episode past eval_max_steps
+            order, n_order, resume = None, n, 0
+            while True:
+                sus = L.Suspend(*[L.ptr(t) for t in (sus_board, sus_meta, sus_total, lists[0], sus_count)])
+                common = (len(hidden), harr, act, ctypes.byref(cfg), int(use_greedy), *[L.ptr(t) for t in streams],
+                          L.ptr(queue), L.ptr(order), n_order, resume, ctypes.byref(sus), n, limit, ctypes.byref(out))
+                if family == "deep":
+                    L.check(self._lib.g2048_deep_eval(L.ptr(packed), *common, self._stream))
+                else:
+                    L.check(self._lib.g2048_sized_eval(self.size, L.ptr(packed), *common,
+                                                       int(self.sized_rollout_max_workgroups), self._stream))
+                k = int(sus_count.item())          # one host sync per launch
+                if k == 0:
+                    break
+                if limit >= most:
+                    hint = "set max_steps" + ("" if self.env_config.use_action_mask else " or use_action_mask=True")
+                    raise RuntimeError(
+                        f"evaluate_batch: {k} episode(s) still running after {limit} steps; playing on would pass "
+                        f"eval_max_steps = {most} -- {hint}")
+                order, n_order, resume = lists[0], k, 1
+                lists.reverse()
+                queue.zero_()
+                sus_count.zero_()
+                limit = min(limit + budget, most)
+        return EvalBatch(lengths=lengths, total_reward=totals,
+                         max_tile=torch.ones(n, dtype=torch.int64, device=dev) << max_e.to(torch.int64),
+                         final_boards=final)
 
     def trajectories_from_batch(self, batch: TrajectoryBatch, with_states: bool = True) -> list[dict[str, Any]]:
         """Convert a device batch to the reference's trajectory dicts (src/reinforce_agent.py:240-247)."""

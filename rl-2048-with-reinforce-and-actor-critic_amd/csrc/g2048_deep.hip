@@ -712,7 +712,10 @@ constexpr uint32_t kNoEpisode = 0xFFFFFFFFu;
 // issued before the choice (32 scattered loads per lane: logits + choice 2.2 k -> 6.5 k cycles, rollout 0.241 ->
 // 0.263 s); the move by line_move_alu instead of the tables (env step 2.5 k -> 3.0 k, 0.241 -> 0.243 s); the output
 // bias from LDS and the fp64 division of k = 3 skipped (0.241 -> 0.242 s).
-template <int OBS, int ACT, int NB>
+// TRAJ = false (g2048_deep_eval): the score-only form -- the same code without the trajectory row (its stores and the
+// row index), so the same episodes; a.tr holds the four per-episode outputs only, and a.cap is the absolute step count
+// at which an episode still running is suspended in this launch (every launch stays bounded).
+template <int OBS, int ACT, int NB, bool TRAJ = true>
 __global__ void __launch_bounds__(NB * 8, NB == 64 ? 1 : 2) deep_rollout_kernel(DeepRollArgs a) {
     static_assert(NB == 32 || (NB == 64 && OBS == G2048_OBS_ONEHOT), "64 slots: one-hot nets");
     typedef typename std::conditional<NB == 64, DeepSmem64, DeepSmem>::type Smem;
@@ -820,12 +823,14 @@ __global__ void __launch_bounds__(NB * 8, NB == 64 ? 1 : 2) deep_rollout_kernel(
             asm volatile("" ::"v"(ov.board), "v"(ov.reward), "v"(ov.flags));
 #endif
             FWD_STAMP(dc, 7);
-            const size_t row = (size_t)t * a.n + ep;
-            a.tr.boards[row] = b;
-            a.tr.actions[row] = (uint8_t)act;
-            a.tr.rewards[row] = ov.reward;
-            a.tr.flags[row] = (uint8_t)ov.flags;
-            if (a.tr.probs) reinterpret_cast<float4*>(a.tr.probs)[row] = make_float4(p[0], p[1], p[2], p[3]);
+            if constexpr (TRAJ) {
+                const size_t row = (size_t)t * a.n + ep;
+                a.tr.boards[row] = b;
+                a.tr.actions[row] = (uint8_t)act;
+                a.tr.rewards[row] = ov.reward;
+                a.tr.flags[row] = (uint8_t)ov.flags;
+                if (a.tr.probs) reinterpret_cast<float4*>(a.tr.probs)[row] = make_float4(p[0], p[1], p[2], p[3]);
+            }
             total += ov.reward;                        // total_reward += float(reward) (src/reinforce_agent.py:233)
             b = ov.board;
             t += 1;
@@ -2152,10 +2157,27 @@ int check_hip() {
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? G2048_OK : dfail(G2048_EHIP, hipGetErrorString(e));
 }
-template <int OBS, int ACT, int NB>
+template <int OBS, int ACT, int NB, bool TRAJ>
 int launch_deep_roll(const DeepRollArgs& a, int grid, hipStream_t s) {
-    hipLaunchKernelGGL((deep_rollout_kernel<OBS, ACT, NB>), dim3(grid), dim3(NB * 8), 0, s, a);
+    hipLaunchKernelGGL((deep_rollout_kernel<OBS, ACT, NB, TRAJ>), dim3(grid), dim3(NB * 8), 0, s, a);
     return check_hip();
+}
+// the grid and the instantiation of g2048_deep_rollout (TRAJ) and g2048_deep_eval (score-only)
+template <bool TRAJ>
+int launch_deep_roll_form(const DeepRollArgs& a, int obs, int activation, int64_t n_order, int cus, hipStream_t s) {
+    if (obs == G2048_OBS_ONEHOT) {   // persistent: one workgroup per CU, 64 slots each
+        int64_t grid = (n_order + 63) / 64;
+        if (grid > (int64_t)cus) grid = cus;
+        return activation == G2048_ACT_RELU ? launch_deep_roll<G2048_OBS_ONEHOT, 0, 64, TRAJ>(a, (int)grid, s)
+                                            : launch_deep_roll<G2048_OBS_ONEHOT, 1, 64, TRAJ>(a, (int)grid, s);
+    }
+    int64_t grid = (n_order + 31) / 32;
+    if (grid > 2 * (int64_t)cus) grid = 2 * (int64_t)cus;   // persistent; the slots refill from the queue
+    if (obs == G2048_OBS_LOG2)
+        return activation == G2048_ACT_RELU ? launch_deep_roll<G2048_OBS_LOG2, 0, 32, TRAJ>(a, (int)grid, s)
+                                            : launch_deep_roll<G2048_OBS_LOG2, 1, 32, TRAJ>(a, (int)grid, s);
+    return activation == G2048_ACT_RELU ? launch_deep_roll<G2048_OBS_RAW, 0, 32, TRAJ>(a, (int)grid, s)
+                                        : launch_deep_roll<G2048_OBS_RAW, 1, 32, TRAJ>(a, (int)grid, s);
 }
 
 }  // namespace
@@ -2300,21 +2322,63 @@ int g2048_deep_rollout(const float* packed, int n_hidden, const int32_t* hidden,
     a.tr = *traj;
     a.n = (uint32_t)n;
     a.cap = (uint32_t)cap;
-    hipStream_t s = (hipStream_t)stream;
-    const int obs = cfg->obs_mode;
-    if (obs == G2048_OBS_ONEHOT) {   // persistent: one workgroup per CU, 64 slots each
-        int64_t grid = (n_order + 63) / 64;
-        if (grid > (int64_t)cus) grid = cus;
-        return activation == G2048_ACT_RELU ? launch_deep_roll<G2048_OBS_ONEHOT, 0, 64>(a, (int)grid, s)
-                                            : launch_deep_roll<G2048_OBS_ONEHOT, 1, 64>(a, (int)grid, s);
-    }
-    int64_t grid = (n_order + 31) / 32;
-    if (grid > 2 * (int64_t)cus) grid = 2 * (int64_t)cus;   // persistent; the slots refill from the queue
-    if (obs == G2048_OBS_LOG2)
-        return activation == G2048_ACT_RELU ? launch_deep_roll<G2048_OBS_LOG2, 0, 32>(a, (int)grid, s)
-                                            : launch_deep_roll<G2048_OBS_LOG2, 1, 32>(a, (int)grid, s);
-    return activation == G2048_ACT_RELU ? launch_deep_roll<G2048_OBS_RAW, 0, 32>(a, (int)grid, s)
-                                        : launch_deep_roll<G2048_OBS_RAW, 1, 32>(a, (int)grid, s);
+    return launch_deep_roll_form<true>(a, cfg->obs_mode, activation, n_order, cus, (hipStream_t)stream);
+}
+
+int g2048_deep_eval(const float* packed, int n_hidden, const int32_t* hidden, int activation, const g2048_env_cfg* cfg,
+                    int greedy, uint64_t* env_state, const uint64_t* env_inc, uint64_t* env_buf, uint64_t* pol_state,
+                    const uint64_t* pol_inc, uint64_t* pol_buf, uint32_t* queue, const int32_t* order, int64_t n_order,
+                    int resume, const g2048_suspend* sus, int64_t n, int64_t step_limit, const g2048_eval_out* out,
+                    void* stream) {
+    int rc = g2048_internal::check_env_cfg(cfg);
+    if (rc) return rc;
+    if (n < 0 || n > (int64_t)0x7FFFFFFF) return dfail(G2048_EINVAL, "n out of range");
+    if (n_order < 0 || n_order > n || (!order && n_order != n) || (resume && !order))
+        return dfail(G2048_EINVAL, "deep eval: order must list n_order <= n episodes (all n when NULL; resume needs a list)");
+    if (step_limit < 1 || step_limit > (int64_t)0x7FFFFFFF)
+        return dfail(G2048_EINVAL, "deep eval: step_limit must be in 1..2^31-1");
+    DeepNet net;
+    if (!deep_layout(n_hidden, hidden, cfg->obs_mode == G2048_OBS_ONEHOT, net))
+        return dfail(G2048_EINVAL, "deep policy: 1..4 hidden layers of 1..256 units");
+    if (activation != G2048_ACT_RELU && activation != G2048_ACT_SIGMOID)
+        return dfail(G2048_EINVAL, "Unsupported activation");
+    if (!packed || !env_state || !env_inc || !env_buf || !pol_state || !pol_inc || !pol_buf || !queue || !sus || !out ||
+        !sus->board || !sus->meta || !sus->total || !sus->list || !sus->count || !out->lengths || !out->totals ||
+        !out->max_tile || !out->final_board)
+        return dfail(G2048_EINVAL, "deep eval: a required buffer is NULL");
+    if (n_order == 0) return G2048_OK;
+    const uint8_t* tab = nullptr;
+    int cus = 256;
+    if ((rc = g2048_internal::device_tables(tab, cus))) return rc;
+    DeepRollArgs a;
+    a.diag = nullptr;                                   // -DG2048_DEEP_DIAG=1 builds: the score-only form takes no stamps
+    a.net = net;
+    a.packed = packed;
+    a.tab = tab;
+    a.rc = g2048_internal::reward_cfg_of(*cfg);
+    a.max_steps = cfg->max_steps;
+    a.obs_scale = cfg->obs_log2_scale;
+    a.use_mask = cfg->use_action_mask;
+    a.greedy = greedy;
+    a.env_rs = env_state;
+    a.env_inc = env_inc;
+    a.env_buf = env_buf;
+    a.pol_rs = pol_state;
+    a.pol_inc = pol_inc;
+    a.pol_buf = pol_buf;
+    a.next = queue;
+    a.order = order;
+    a.n_order = (uint32_t)n_order;
+    a.resume = resume;
+    a.sus = *sus;
+    a.tr = g2048_traj{};                                // no rows: the score-only kernels never read these
+    a.tr.lengths = out->lengths;
+    a.tr.totals = out->totals;
+    a.tr.max_tile = out->max_tile;
+    a.tr.final_board = out->final_board;
+    a.n = (uint32_t)n;
+    a.cap = (uint32_t)step_limit;                       // the step count at which a running episode is suspended
+    return launch_deep_roll_form<false>(a, cfg->obs_mode, activation, n_order, cus, (hipStream_t)stream);
 }
 
 int g2048_deep_hidden(const float* packed, int n_hidden, const int32_t* hidden, int activation, int obs_mode,

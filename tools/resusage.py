@@ -46,10 +46,10 @@ for line in r.stderr.splitlines():
     elif cur is not None and ":" in txt:
         k, v = txt.split(":", 1)
         cur[k.strip()] = v.strip()
-print(f"{'VGPR':>5} {'AGPR':>5} {'vspill':>6} {'sspill':>6} {'scratch':>7} {'occ':>3} {'LDS':>7}  kernel")
+print(f"{'VGPR':>5} {'AGPR':>5} {'SGPR':>5} {'vspill':>6} {'sspill':>6} {'scratch':>7} {'occ':>3} {'LDS':>7}  kernel")
 for c in rows:
     if pat and pat not in c["name"]:
         continue
-    print(f"{c.get('VGPRs', ''):>5} {c.get('AGPRs', ''):>5} {c.get('VGPRs Spill', ''):>6} {c.get('SGPRs Spill', ''):>6} "
+    print(f"{c.get('VGPRs', ''):>5} {c.get('AGPRs', ''):>5} {c.get('TotalSGPRs', c.get('SGPRs', '')):>5} {c.get('VGPRs Spill', ''):>6} {c.get('SGPRs Spill', ''):>6} "
           f"{c.get('ScratchSize [bytes/lane]', ''):>7} {c.get('Occupancy [waves/SIMD]', ''):>3} "
           f"{c.get('LDS Size [bytes/block]', ''):>7}  {c['name'][:110]}")
