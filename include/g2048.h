@@ -439,4 +439,8 @@ int g2048_onehot_dw1(const uint64_t* boards, const float* d1, int h1, int64_t m,
 /* board sizes 2..8: the g2048_sized_* entry points (ABI 17), part of this interface */
 #include "g2048_sized.h"
 
+/* whole episodes of a scripted player (priority order / uniform over the valid moves): additive entry points of ABI
+ * 17, part of this interface */
+#include "g2048_scripted.h"
+
 #endif /* G2048_H */

@@ -26,7 +26,10 @@ SOURCES = [SRC, os.path.join(PKG_DIR, "csrc", "g2048_policy.hip"), os.path.join(
            # the score-only (no trajectory row) instantiations of the persistent rollout kernels, in units of their
            # own so that they compile beside the trajectory forms
            os.path.join(PKG_DIR, "csrc", "g2048_rollout_eval.hip"),
-           os.path.join(PKG_DIR, "csrc", "g2048_sized_eval.hip")]
+           os.path.join(PKG_DIR, "csrc", "g2048_sized_eval.hip"),
+           # whole episodes of a scripted player (no net): 4 x 4 and sizes 2..8
+           os.path.join(PKG_DIR, "csrc", "g2048_scripted.hip"),
+           os.path.join(PKG_DIR, "csrc", "g2048_sized_scripted.hip")]
 INCLUDE = os.path.join(REPO_ROOT, "include")
 ABI_VERSION = 17
 DEEP_MAX_HIDDEN = 4
@@ -41,6 +44,9 @@ F_OVERFLOW, F_RESET, F_INACTIVE, F_BADACTION = 0x10, 0x20, 0x40, 0x80
 LS_STEP_MASK, LS_MAXT_SHIFT, LS_ACTIVE, LS_HAS_U32 = 0x000FFFFF, 20, 0x02000000, 0x04000000
 MAX_STEPS_LIMIT = 0x000FFFFF
 G2048_OK, G2048_EINVAL, G2048_EHIP, G2048_ENOINIT = 0, 1, 2, 3
+# include/g2048_scripted.h
+SCRIPT_PRIORITY, SCRIPT_UNIFORM = 0, 1
+SCRIPT_BLOCK = 256
 
 
 CSRC = os.path.join(PKG_DIR, "csrc")
@@ -74,7 +80,7 @@ def _object_for(src: str, flags: list[str]) -> str:
     h.update(_compiler_id().encode())
     hdrs = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".inc")))
     for f in [src] + hdrs + [os.path.join(INCLUDE, "g2048.h"), os.path.join(INCLUDE, "g2048_sized.h"),
-                                os.path.join(INCLUDE, "g2048_eval.h")]:
+                                os.path.join(INCLUDE, "g2048_eval.h"), os.path.join(INCLUDE, "g2048_scripted.h")]:
         with open(f, "rb") as fh:
             h.update(fh.read())
     return os.path.join(BUILD_DIR, f"{os.path.splitext(os.path.basename(src))[0]}-{h.hexdigest()[:16]}.o")
@@ -163,6 +169,11 @@ class EvalOut(ctypes.Structure):
     _fields_ = [(name, ctypes.c_void_p) for name in ("lengths", "totals", "max_tile", "final_board")]
 
 
+class Script(ctypes.Structure):
+    """g2048_script: the scripted player of a launch (kind SCRIPT_*; order: PRIORITY's permutation of 0..3)."""
+    _fields_ = [("kind", ctypes.c_int32), ("order", ctypes.c_uint8 * 4)]
+
+
 _lib = None
 _lock = threading.RLock()
 _inited_devices: set[int] = set()
@@ -249,7 +260,15 @@ def _declare(L):
                                   P(Suspend), i64, i64, P(EvalOut), vp]
     L.g2048_sized_eval.argtypes = [i32, vp, i32, vp, i32, P(EnvCfg), i32, vp, vp, vp, vp, vp, vp, vp, vp, i64, i32,
                                    P(Suspend), i64, i64, P(EvalOut), i32, vp]
-    for name in SIZED_SYMBOLS + EVAL_SYMBOLS:
+    L.g2048_scripted_rollout.argtypes = [P(Script), P(EnvCfg), vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, P(Suspend), i64,
+                                         i64, P(Traj), i32, vp]
+    L.g2048_scripted_eval.argtypes = [P(Script), P(EnvCfg), vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, P(Suspend), i64,
+                                      i64, P(EvalOut), i32, vp]
+    L.g2048_sized_scripted_rollout.argtypes = [i32, P(Script), P(EnvCfg), vp, vp, vp, vp, vp, vp, vp, vp, i64, i32,
+                                               P(Suspend), i64, i64, P(Traj), i64, i32, vp]
+    L.g2048_sized_scripted_eval.argtypes = [i32, P(Script), P(EnvCfg), vp, vp, vp, vp, vp, vp, vp, vp, i64, i32,
+                                            P(Suspend), i64, i64, P(EvalOut), i32, vp]
+    for name in SIZED_SYMBOLS + EVAL_SYMBOLS + SCRIPTED_SYMBOLS:
         getattr(L, name).restype = ctypes.c_int
     for name in ("g2048_init", "g2048_seed_pcg64", "g2048_reset", "g2048_step", "g2048_obs", "g2048_move",
                  "g2048_sample", "g2048_returns", "g2048_symmetries", "g2048_policy_pack", "g2048_policy",
@@ -280,6 +299,10 @@ SIZED_SYMBOLS = ("g2048_sized_words", "g2048_sized_reset", "g2048_sized_step", "
 # include/g2048_eval.h (included by g2048.h): score-only rollouts of the 4 x 4 families (g2048_sized_eval, their
 # counterpart for sizes 2..8, is declared with the sized entry points)
 EVAL_SYMBOLS = ("g2048_rollout_eval", "g2048_deep_eval")
+
+# include/g2048_scripted.h (included by g2048.h): whole episodes of a scripted player
+SCRIPTED_SYMBOLS = ("g2048_scripted_rollout", "g2048_scripted_eval", "g2048_sized_scripted_rollout",
+                    "g2048_sized_scripted_eval")
 
 
 def lib():

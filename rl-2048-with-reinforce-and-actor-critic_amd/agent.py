@@ -1361,13 +1361,21 @@ class ReinforceAgent:
 
     @torch.no_grad()
     def rollout_batch(self, env_seeds, policy_seeds, use_greedy: bool = False, rng: str = "pcg64",
-                      check_every: int = 8, record_probs: bool = False) -> TrajectoryBatch:
+                      check_every: int = 8, record_probs: bool = False, action_gen=None) -> TrajectoryBatch:
         """Play one episode per lane (env.reset(seed=env_seeds[i]), policy stream default_rng(policy_seeds[i]))
         until every lane terminates or truncates -- the batched equivalent of calling run_episode for each
-        (env_seed, policy_seed) pair (runner.py:587-591).  Everything stays on the device."""
+        (env_seed, policy_seed) pair (runner.py:587-591).  Everything stays on the device.
+        action_gen: a PriorityPolicy / UniformPolicy plays the episodes instead of the net (run_episode's action_gen,
+        batched: g2048_scripted_rollout); use_greedy is then ignored, as the reference ignores it when action_fn
+        answers."""
         n = len(env_seeds)
         if len(policy_seeds) != n:
             raise ValueError("env_seeds and policy_seeds must have the same length")
+        if action_gen is not None:
+            self._check_scripted(action_gen, rng, record_probs)
+            name = "g2048_sized_scripted_rollout" if self._sized else "g2048_scripted_rollout"
+            self._paths["rollout"] = name + " (persistent launches, one episode per lane, suspended episodes resumed)"
+            return self._rollout_scripted(env_seeds, policy_seeds, action_gen)
         spec = self._fused_policy_spec()
         if spec is not None and rng == "pcg64" and self.env_config.max_steps is not None and self.use_fused_rollout:
             self._paths["rollout"] = "g2048_rollout (one persistent launch)"
@@ -1714,14 +1722,22 @@ class ReinforceAgent:
     eval_step_budget = 4096
     eval_max_steps = 1 << 20
 
-    def evaluate_batch(self, env_seeds, policy_seeds, use_greedy: bool = True, rng: str = "pcg64") -> EvalBatch:
+    def evaluate_batch(self, env_seeds, policy_seeds, use_greedy: bool = True, rng: str = "pcg64",
+                       action_gen=None) -> EvalBatch:
         """The episodes rollout_batch plays for these seeds under the same agent settings, keeping only what an
         evaluation reads of them (lengths, total_reward, max_tile, final_boards): no trajectory rows, so memory is O(n)
         whatever the episodes' lengths.  The family is chosen by rollout_batch's own tests in its order; what no
-        persistent kernel covers goes through rollout_batch itself.  last_paths()["eval"] names what ran."""
+        persistent kernel covers goes through rollout_batch itself.  last_paths()["eval"] names what ran.
+        action_gen: as rollout_batch's (g2048_scripted_eval)."""
         n = len(env_seeds)
         if len(policy_seeds) != n:
             raise ValueError("env_seeds and policy_seeds must have the same length")
+        if action_gen is not None:
+            self._check_scripted(action_gen, rng, False)
+            name = "g2048_sized_scripted_eval" if self._sized else "g2048_scripted_eval"
+            self._paths["eval"] = name + (" (persistent launches, one episode per lane, no trajectory rows, suspended "
+                                          "episodes resumed)")
+            return self._evaluate_scripted(env_seeds, policy_seeds, action_gen)
         spec = self._fused_policy_spec()
         if spec is not None and rng == "pcg64" and self.env_config.max_steps is not None and self.use_fused_rollout:
             self._paths["eval"] = "g2048_rollout_eval (one persistent launch, no trajectory rows)"
@@ -1817,6 +1833,169 @@ class ReinforceAgent:
                          max_tile=torch.ones(n, dtype=torch.int64, device=dev) << max_e.to(torch.int64),
                          final_boards=final)
 
+    # Scripted play (rollout_batch / evaluate_batch with action_gen = PriorityPolicy / UniformPolicy; no net, so the
+    # use_fused_* switches do not apply): the grid cap of g2048_scripted_* (0: what n needs, at most what is resident),
+    # the first trajectory capacity (max_steps when that is fewer rows; doubled while episodes run past it) and the
+    # most rows it may grow to.  evaluate_batch uses eval_step_budget / eval_max_steps.  Class attributes, as above.
+    scripted_max_workgroups = 0
+    scripted_rollout_cap0 = 512
+    scripted_rollout_max_rows = 1 << 24
+
+    def _check_scripted(self, action_gen, rng: str, record_probs: bool) -> None:
+        """The refusals of the batched scripted path, before any device call."""
+        from .policies import PriorityPolicy, UniformPolicy
+
+        if not isinstance(action_gen, (PriorityPolicy, UniformPolicy)):
+            raise TypeError(
+                f"action_gen must be a PriorityPolicy or a UniformPolicy on the batched path (got "
+                f"{type(action_gen).__name__}); run_episode(env_seed, policy_seed, action_gen=...) is the host path "
+                f"for arbitrary callables")
+        if rng != "pcg64":
+            raise ValueError(f'scripted play (action_gen) runs on the PCG64 streams only (rng="pcg64"), got rng={rng!r}')
+        if record_probs:
+            raise ValueError("record_probs=True with an action_gen: a scripted player has no probabilities to record")
+        if isinstance(action_gen, PriorityPolicy) and not self.env_config.use_action_mask:
+            raise ValueError("a PriorityPolicy needs env_config.use_action_mask=True on the batched path (its choice is "
+                             "read off the action mask)")
+
+    def _scripted_buffers(self, env_seeds, policy_seeds):
+        """The per-episode buffers both scripted host loops share: the two PCG64 streams, the four outputs and the
+        suspend state (board planes [W, n] for sizes other than 4)."""
+        from .vec_env import _as_u64_seeds
+
+        n = len(env_seeds)
+        dev = self.device
+        W = int(self._lib.g2048_sized_words(self.size)) if self._sized else 1
+        planes = (lambda: torch.empty(W, n, dtype=torch.int64, device=dev)) if self._sized else \
+                 (lambda: torch.empty(n, dtype=torch.int64, device=dev))
+        es = _as_u64_seeds(_seed_seq(env_seeds), n, 0, dev)
+        ps = _as_u64_seeds(_seed_seq(policy_seeds), n, 0, dev)
+        streams = []
+        for seeds in (es, ps):
+            st = torch.empty(2 * n, dtype=torch.int64, device=dev)
+            inc = torch.empty(2 * n, dtype=torch.int64, device=dev)
+            buf = torch.empty(n, dtype=torch.int64, device=dev)
+            L.check(self._lib.g2048_seed_pcg64(L.ptr(seeds), L.ptr(st), L.ptr(inc), L.ptr(buf), n, self._stream))
+            streams += [st, inc, buf]
+        lengths = torch.empty(n, dtype=torch.int32, device=dev)
+        totals = torch.empty(n, dtype=torch.float64, device=dev)
+        max_e = torch.empty(n, dtype=torch.uint8, device=dev)
+        final = planes()
+        sus_board = planes()
+        sus_meta = torch.empty(3 * n, dtype=torch.int32, device=dev)
+        sus_total = torch.empty(n, dtype=torch.float64, device=dev)
+        sus_count = torch.zeros(1, dtype=torch.int32, device=dev)
+        queue = torch.zeros(1, dtype=torch.int32, device=dev)
+        return W, streams, (lengths, totals, max_e, final), (sus_board, sus_meta, sus_total), sus_count, queue
+
+    def _rollout_scripted(self, env_seeds, policy_seeds, policy) -> TrajectoryBatch:
+        """rollout_batch for a scripted player (g2048_scripted_rollout / g2048_sized_scripted_rollout): the suspend /
+        grow / resume loop and the refusal of _rollout_deep / _rollout_sized around a kernel that needs no net.  The
+        batch has the fields, shapes and dtypes of the net-driven paths' (probs None)."""
+        from .config import env_cfg_struct
+
+        n = len(env_seeds)
+        dev = self.device
+        sized = self._sized
+        W, streams, outs, sus_state, sus_count, queue = self._scripted_buffers(env_seeds, policy_seeds)
+        lengths, totals, max_e, final = outs
+        ms = self.env_config.max_steps
+        cap0 = int(self.scripted_rollout_cap0)
+        cap = max(min(int(ms), cap0) if ms is not None else cap0, 1)
+        bshape = (lambda rows: (W, rows, n)) if sized else (lambda rows: (rows, n))
+        boards = torch.empty(bshape(cap), dtype=torch.int64, device=dev)
+        actions = torch.zeros(cap, n, dtype=torch.uint8, device=dev)
+        rewards = torch.zeros(cap, n, dtype=torch.float64, device=dev)
+        flags = torch.full((cap, n), L.F_INACTIVE, dtype=torch.uint8, device=dev)
+        sus_list = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+        sus = L.Suspend(*[L.ptr(t) for t in (*sus_state, sus_list, sus_count)])
+        cfg = env_cfg_struct(self.env_config)
+        script = policy._script()
+        order, n_order, resume = None, n, 0
+        while True:
+            traj = L.Traj(*[L.ptr(t) for t in (boards, actions, rewards, flags, None, lengths, totals, max_e, final)])
+            common = (ctypes.byref(script), ctypes.byref(cfg), *[L.ptr(t) for t in streams], L.ptr(queue), L.ptr(order),
+                      n_order, resume, ctypes.byref(sus), n, cap, ctypes.byref(traj))
+            if sized:
+                L.check(self._lib.g2048_sized_scripted_rollout(self.size, *common, cap * n,
+                                                               int(self.scripted_max_workgroups), self._stream))
+            else:
+                L.check(self._lib.g2048_scripted_rollout(*common, int(self.scripted_max_workgroups), self._stream))
+            k = int(sus_count.item())          # one host sync per launch
+            if k == 0:
+                break
+            order, n_order, resume = sus_list[:k].clone(), k, 1
+            queue.zero_()
+            sus_count.zero_()
+            grow = cap if ms is None else max(min(cap, int(ms) - cap), 1)   # never past max_steps rows
+            # as _rollout_deep: an episode that never ends must not run the device out of memory
+            row_bytes = n * (8 * W + 1 + 8 + 1)
+            free_b = 1 << 62
+            if dev.type == "cuda":
+                free_b = (torch.cuda.mem_get_info(dev)[0] + torch.cuda.memory_reserved(dev) -
+                          torch.cuda.memory_allocated(dev))
+            if cap + grow > self.scripted_rollout_max_rows or (cap + grow) * row_bytes > free_b + cap * row_bytes // 2:
+                hint = "set max_steps" + ("" if self.env_config.use_action_mask else " or use_action_mask=True")
+                raise RuntimeError(
+                    f"rollout_batch (max_steps=None): {k} episode(s) still running after {cap} steps; growing the "
+                    f"[T, n] trajectory buffer to {cap + grow} rows needs {(cap + grow) * row_bytes / 2**30:.1f} GiB "
+                    f"(free: {free_b / 2**30:.1f} GiB, row limit {self.scripted_rollout_max_rows}) -- {hint}")
+            boards = torch.cat([boards, torch.empty(bshape(grow), dtype=torch.int64, device=dev)], dim=1 if sized else 0)
+            actions = torch.cat([actions, torch.zeros(grow, n, dtype=torch.uint8, device=dev)])
+            rewards = torch.cat([rewards, torch.zeros(grow, n, dtype=torch.float64, device=dev)])
+            flags = torch.cat([flags, torch.full((grow, n), L.F_INACTIVE, dtype=torch.uint8, device=dev)])
+            cap += grow
+        T = int(lengths.max().item()) if n else 0
+        return TrajectoryBatch(boards=boards[:, :T] if sized else boards[:T], actions=actions[:T], rewards=rewards[:T],
+                               flags=flags[:T], lengths=lengths, total_reward=totals,
+                               max_tile=torch.ones(n, dtype=torch.int64, device=dev) << max_e.to(torch.int64),
+                               final_boards=final, probs=None)
+
+    def _evaluate_scripted(self, env_seeds, policy_seeds, policy) -> EvalBatch:
+        """evaluate_batch for a scripted player (g2048_scripted_eval / g2048_sized_scripted_eval): _evaluate_persistent's
+        loop -- relaunch what the kernel suspended every eval_step_budget steps, two episode lists, refuse past
+        eval_max_steps; nothing grows between launches."""
+        from .config import env_cfg_struct
+
+        n = len(env_seeds)
+        dev = self.device
+        _, streams, outs, sus_state, sus_count, queue = self._scripted_buffers(env_seeds, policy_seeds)
+        lengths, totals, max_e, final = outs
+        out = L.EvalOut(*[L.ptr(t) for t in outs])
+        # two episode lists: the one a launch reads as its order and the one it fills with what it suspends
+        lists = [torch.empty(max(n, 1), dtype=torch.int32, device=dev) for _ in range(2)]
+        cfg = env_cfg_struct(self.env_config)
+        script = policy._script()
+        budget = max(int(self.eval_step_budget), 1)
+        most = max(int(self.eval_max_steps), 1)
+        limit = min(budget, most)                   # no launch plays an episode past eval_max_steps
+        order, n_order, resume = None, n, 0
+        while True:
+            sus = L.Suspend(*[L.ptr(t) for t in (*sus_state, lists[0], sus_count)])
+            common = (ctypes.byref(script), ctypes.byref(cfg), *[L.ptr(t) for t in streams], L.ptr(queue), L.ptr(order),
+                      n_order, resume, ctypes.byref(sus), n, limit, ctypes.byref(out),
+                      int(self.scripted_max_workgroups), self._stream)
+            if self._sized:
+                L.check(self._lib.g2048_sized_scripted_eval(self.size, *common))
+            else:
+                L.check(self._lib.g2048_scripted_eval(*common))
+            k = int(sus_count.item())          # one host sync per launch
+            if k == 0:
+                break
+            if limit >= most:
+                hint = "set max_steps" + ("" if self.env_config.use_action_mask else " or use_action_mask=True")
+                raise RuntimeError(
+                    f"evaluate_batch: {k} episode(s) still running after {limit} steps; playing on would pass "
+                    f"eval_max_steps = {most} -- {hint}")
+            order, n_order, resume = lists[0], k, 1
+            lists.reverse()
+            queue.zero_()
+            sus_count.zero_()
+            limit = min(limit + budget, most)
+        return EvalBatch(lengths=lengths, total_reward=totals,
+                         max_tile=torch.ones(n, dtype=torch.int64, device=dev) << max_e.to(torch.int64),
+                         final_boards=final)
+
     def trajectories_from_batch(self, batch: TrajectoryBatch, with_states: bool = True) -> list[dict[str, Any]]:
         """Convert a device batch to the reference's trajectory dicts (src/reinforce_agent.py:240-247)."""
         n, T = batch.n, batch.T
@@ -1858,9 +2037,18 @@ class ReinforceAgent:
     def run_episode(self, env_seed: int, policy_seed: int, action_gen: Callable | None = None,
                     use_greedy: bool = False) -> dict[str, Any]:
         """src/reinforce_agent.py:195-252.  Without action_gen the episode runs on the device lane path (same
-        spawn and policy streams as the reference); with action_gen it steps the drop-in env from the host."""
+        spawn and policy streams as the reference); with action_gen it steps the drop-in env from the host -- except
+        for a UniformPolicy, or a PriorityPolicy on an env with an action mask, which the device plays
+        (rollout_batch's action_gen).  A PriorityPolicy on a mask-less env is a plain callable here: it fails on the
+        None mask and select_action falls back to the net, as the reference does."""
         if action_gen is None:
             return self.trajectories_from_batch(self.rollout_batch([env_seed], [policy_seed], use_greedy))[0]
+        from .policies import PriorityPolicy, UniformPolicy
+
+        if isinstance(action_gen, UniformPolicy) or (isinstance(action_gen, PriorityPolicy) and
+                                                     self.env_config.use_action_mask):
+            return self.trajectories_from_batch(
+                self.rollout_batch([env_seed], [policy_seed], action_gen=action_gen))[0]
         from .env import Game2048Env
 
         env = self.env if self.env is not None else Game2048Env(self.env_config, device=self.device)

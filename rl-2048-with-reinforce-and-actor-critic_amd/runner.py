@@ -302,10 +302,12 @@ def training(device=None) -> List[Dict[str, Any]]:
 
 # ---------------------------------------------------------------------------------------------- evaluation
 def evaluation_loop(agent: ReinforceAgent, eval_cfg: Dict[str, Any], chunk: int = 65536,
-                    score_only: bool = False) -> Dict[str, Any]:
+                    score_only: bool = False, action_gen=None) -> Dict[str, Any]:
     """runner.py:737-828: num_episodes episodes with fixed seed streams (greedy by default), batched.
     score_only: play them through agent.evaluate_batch (no trajectory rows: memory does not depend on the episodes'
-    lengths) instead of rollout_batch; the same episodes and the same summary."""
+    lengths) instead of rollout_batch; the same episodes and the same summary.
+    action_gen: a PriorityPolicy / UniformPolicy plays the episodes instead of the agent's net (the baselines a
+    trained net is judged against); passed through to rollout_batch / evaluate_batch."""
     n = int(eval_cfg["num_episodes"])
     greedy = bool(eval_cfg.get("use_greedy", True))
     env_seeds = SeedStream(int(eval_cfg["env_base_seed"])).take_array(n)
@@ -315,7 +317,8 @@ def evaluation_loop(agent: ReinforceAgent, eval_cfg: Dict[str, Any], chunk: int 
         e, p = env_seeds[s:s + chunk], pol_seeds[s:s + chunk]
         lo, hi = _shard(len(e))
         play = agent.evaluate_batch if score_only else agent.rollout_batch
-        b = play(e[lo:hi], p[lo:hi], use_greedy=greedy)
+        scripted = {} if action_gen is None else {"action_gen": action_gen}
+        b = play(e[lo:hi], p[lo:hi], use_greedy=greedy, **scripted)
         b.shard_sizes = dp.shard_sizes(len(e), dp.world()[1])
         t, m = _global_episode_stats(b)
         totals.append(t)
