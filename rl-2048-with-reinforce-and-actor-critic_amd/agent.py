@@ -27,12 +27,13 @@ import ctypes
 import logging
 import os
 from dataclasses import dataclass
-from typing import Any, Callable, Literal
+from typing import Any, Callable, Literal, NamedTuple
 
 import numpy as np
 import torch
 from . import _lib as L
 from . import dp
+from . import rollouts
 from .config import check_size, Game2048EnvConfig, obs_width
 from .mlp import (MLPConfig, encode_observation, forward_logits, init_model_params, load_model_params, mlp_backward_,
                   mlp_forward_kept,
@@ -44,6 +45,18 @@ OptimizerType = Literal["sgd", "adam"]
 CriticLossType = Literal["mse", "huber"]
 
 _OBS_CODE = {"raw": L.OBS_RAW, "log2": L.OBS_LOG2, "onehot": L.OBS_ONEHOT}
+
+
+class _Family(NamedTuple):
+    """One family of persistent whole-episode kernels (ReinforceAgent._PERSISTENT)."""
+    rollout: str            # the entry point that records trajectory rows
+    evaluate: str           # its score-only form
+    rollout_path: str       # what last_paths() says of either
+    eval_path: str
+    tuning: str | None      # prefix of the agent's <prefix>_cap0 / <prefix>_max_rows; None: max_steps bounds the rows
+    grid_cap: str | None    # the agent attribute holding the grid cap; None: the entry points take none
+    sized: bool = False     # board sizes other than 4: size argument, [W, ...] board planes, a plane stride
+    scripted: bool = False  # played by a PriorityPolicy / UniformPolicy instead of a net
 
 
 @dataclass
@@ -103,11 +116,6 @@ class EvalBatch:
     @property
     def n(self) -> int:
         return int(self.lengths.numel())
-
-
-def _seed_seq(seeds):
-    """A batch of episode seeds as a tensor / numpy array (kept: the fast conversion path) or a list."""
-    return seeds if isinstance(seeds, (torch.Tensor, np.ndarray)) else list(seeds)
 
 
 def _render_values(vals: np.ndarray) -> str:
@@ -504,41 +512,15 @@ class ReinforceAgent:
             return None
         return h1, h2, act
 
-    def _deep_spec(self, params=None, out_dim: int = 4):
-        """(obs code, hidden sizes, activation code, int32 ctypes array of the sizes) when the net is covered by the
-        any-depth kernels of g2048_deep.hip (1..4 hidden layers of 1..256 units, ReLU / Sigmoid, fp32 on this
-        device, log2 / raw / one-hot obs), else None."""
-        if self._sized:      # input_dim is N*N(*17) here: a 3 x 3 net would otherwise pass the width check below
-            return None
-        params = self.params if params is None else params
-        Ws, bs = params["W"], params["b"]
-        nh = len(Ws) - 1
-        act = {"ReLU": L.ACT_RELU, "Sigmoid": L.ACT_SIGMOID}.get(self.mlp_config.activation)
-        if act is None or not (1 <= nh <= L.DEEP_MAX_HIDDEN) or len(bs) != len(Ws):
-            return None
-        hidden = tuple(int(W.shape[1]) for W in Ws[:-1])
-        if tuple(Ws[0].shape)[0] != self.input_dim or tuple(Ws[-1].shape)[1] != out_dim or \
-                not all(1 <= h <= 256 for h in hidden):
-            return None
-        if any(tuple(Ws[l].shape)[0] != hidden[l - 1] for l in range(1, nh + 1)):
-            return None
-        if any(t.dtype != torch.float32 or t.device != self.device for t in Ws + bs):
-            return None
-        return (_OBS_CODE[self.env_config.obs_mode], hidden, act, (ctypes.c_int32 * nh)(*hidden))
-
-    def _sized_spec(self, params=None, out_dim: int = 4):
-        """_deep_spec for board sizes other than 4: (obs code, hidden sizes, activation code, int32 ctypes array of
-        the sizes) when g2048_sized_policy covers the net (1..4 hidden layers of 1..256 units, ReLU / Sigmoid, fp32 on
-        this device, W[0] with input_dim = N*N(*17) rows), else None."""
-        if not self._sized:
-            return None
+    def _any_depth_spec(self, params, out_dim: int):
+        """What _deep_spec and _sized_spec both ask of a net: 1..4 hidden layers of 1..256 units chained from
+        input_dim to out_dim, ReLU / Sigmoid, fp32 on this device."""
         params = self.params if params is None else params
         Ws, bs = params["W"], params["b"]
         nh = len(Ws) - 1
         act = {"ReLU": L.ACT_RELU, "Sigmoid": L.ACT_SIGMOID}.get(self.mlp_config.activation)
         obs_code = _OBS_CODE.get(self.env_config.obs_mode)
-        if act is None or obs_code not in (L.OBS_RAW, L.OBS_LOG2, L.OBS_ONEHOT) or \
-                not (1 <= nh <= L.DEEP_MAX_HIDDEN) or len(bs) != len(Ws):
+        if act is None or obs_code is None or not (1 <= nh <= L.DEEP_MAX_HIDDEN) or len(bs) != len(Ws):
             return None
         hidden = tuple(int(W.shape[1]) for W in Ws[:-1])
         if tuple(Ws[0].shape)[0] != self.input_dim or tuple(Ws[-1].shape)[1] != out_dim or \
@@ -548,50 +530,52 @@ class ReinforceAgent:
             return None
         if any(t.dtype != torch.float32 or t.device != self.device for t in Ws + bs):
             return None
-        harr = (ctypes.c_int32 * nh)(*hidden)
-        if int(self._lib.g2048_sized_policy_packed_size(self.size, obs_code, nh, harr)) < 0:
+        return (obs_code, hidden, act, (ctypes.c_int32 * nh)(*hidden))
+
+    def _deep_spec(self, params=None, out_dim: int = 4):
+        """(obs code, hidden sizes, activation code, int32 ctypes array of the sizes) when the net is covered by the
+        any-depth kernels of g2048_deep.hip (1..4 hidden layers of 1..256 units, ReLU / Sigmoid, fp32 on this
+        device, log2 / raw / one-hot obs), else None."""
+        if self._sized:      # input_dim is N*N(*17) here: a 3 x 3 net would otherwise pass the width check
             return None
-        return (obs_code, hidden, act, harr)
+        return self._any_depth_spec(params, out_dim)
+
+    def _sized_spec(self, params=None, out_dim: int = 4):
+        """_deep_spec for board sizes other than 4: the same tuple when g2048_sized_policy covers the net (W[0] with
+        input_dim = N*N(*17) rows, and a packed image that fits the kernel), else None."""
+        spec = self._any_depth_spec(params, out_dim) if self._sized else None
+        if spec is None or \
+                int(self._lib.g2048_sized_policy_packed_size(self.size, spec[0], len(spec[1]), spec[3])) < 0:
+            return None
+        return spec
+
+    def _pack_any_depth(self, params, spec, slot: str, out_dim: int, sized: bool) -> torch.Tensor:
+        """g2048_deep_pack / g2048_sized_pack of a net, cached per slot until a parameter tensor changes."""
+        Ws, bs = params["W"], params["b"]
+        key = (self._params_version,) + tuple((t.data_ptr(), t._version) for t in Ws + bs)
+        entry = self._pack_cache.setdefault(slot + ("/sized" if sized else "/deep"), [None, None, None])
+        if key != entry[1]:
+            obs_code, hidden, _, harr = spec
+            net = (obs_code, len(hidden), harr)
+            size = int(self._lib.g2048_sized_policy_packed_size(self.size, *net) if sized else
+                       self._lib.g2048_deep_packed_size(*net))
+            if entry[0] is None or entry[0].numel() < size:
+                entry[0] = torch.empty(size, dtype=torch.float32, device=self.device)
+            ws = [t.contiguous() for t in Ws]
+            bb = [t.contiguous() for t in bs]
+            wp = (ctypes.c_void_p * len(ws))(*[t.data_ptr() for t in ws])
+            bp = (ctypes.c_void_p * len(bb))(*[t.data_ptr() for t in bb])
+            tail = (wp, bp, *net, out_dim, L.ptr(entry[0]), size, self._stream)
+            L.check(self._lib.g2048_sized_pack(self.size, *tail) if sized else self._lib.g2048_deep_pack(*tail))
+            entry[1] = key
+            entry[2] = (ws, bb)      # keep the contiguous copies alive until the (stream-ordered) pack has run
+        return entry[0]
 
     def _pack_sized(self, params, sspec, slot: str, out_dim: int) -> torch.Tensor:
-        """g2048_sized_pack of a net, cached per slot until a parameter tensor changes (as _pack_deep)."""
-        Ws, bs = params["W"], params["b"]
-        key = (self._params_version,) + tuple((t.data_ptr(), t._version) for t in Ws + bs)
-        entry = self._pack_cache.setdefault(slot + "/sized", [None, None, None])
-        if key != entry[1]:
-            obs_code, hidden, _, harr = sspec
-            size = int(self._lib.g2048_sized_policy_packed_size(self.size, obs_code, len(hidden), harr))
-            if entry[0] is None or entry[0].numel() < size:
-                entry[0] = torch.empty(size, dtype=torch.float32, device=self.device)
-            ws = [t.contiguous() for t in Ws]
-            bb = [t.contiguous() for t in bs]
-            wp = (ctypes.c_void_p * len(ws))(*[t.data_ptr() for t in ws])
-            bp = (ctypes.c_void_p * len(bb))(*[t.data_ptr() for t in bb])
-            L.check(self._lib.g2048_sized_pack(self.size, wp, bp, obs_code, len(hidden), harr, out_dim,
-                                               L.ptr(entry[0]), size, self._stream))
-            entry[1] = key
-            entry[2] = (ws, bb)      # keep the contiguous copies alive until the (stream-ordered) pack has run
-        return entry[0]
+        return self._pack_any_depth(params, sspec, slot, out_dim, True)
 
     def _pack_deep(self, params, dspec, slot: str, out_dim: int) -> torch.Tensor:
-        """g2048_deep_pack of a net, cached per slot until a parameter tensor changes."""
-        Ws, bs = params["W"], params["b"]
-        key = (self._params_version,) + tuple((t.data_ptr(), t._version) for t in Ws + bs)
-        entry = self._pack_cache.setdefault(slot + "/deep", [None, None, None])
-        if key != entry[1]:
-            obs_code, hidden, _, harr = dspec
-            size = int(self._lib.g2048_deep_packed_size(obs_code, len(hidden), harr))
-            if entry[0] is None or entry[0].numel() < size:
-                entry[0] = torch.empty(size, dtype=torch.float32, device=self.device)
-            ws = [t.contiguous() for t in Ws]
-            bb = [t.contiguous() for t in bs]
-            wp = (ctypes.c_void_p * len(ws))(*[t.data_ptr() for t in ws])
-            bp = (ctypes.c_void_p * len(bb))(*[t.data_ptr() for t in bb])
-            L.check(self._lib.g2048_deep_pack(wp, bp, obs_code, len(hidden), harr, out_dim, L.ptr(entry[0]), size,
-                                              self._stream))
-            entry[1] = key
-            entry[2] = (ws, bb)      # keep the contiguous copies alive until the (stream-ordered) pack has run
-        return entry[0]
+        return self._pack_any_depth(params, dspec, slot, out_dim, False)
 
     def _deep_forward(self, params, dspec, slot: str, boards: torch.Tensor, out_dim: int) -> torch.Tensor:
         """forward_logits of the boards through g2048_deep_policy (forward only): [m, 4] (a value head in column 0)."""
@@ -1372,25 +1356,16 @@ class ReinforceAgent:
         if len(policy_seeds) != n:
             raise ValueError("env_seeds and policy_seeds must have the same length")
         if action_gen is not None:
-            self._check_scripted(action_gen, rng, record_probs)
-            name = "g2048_sized_scripted_rollout" if self._sized else "g2048_scripted_rollout"
-            self._paths["rollout"] = name + " (persistent launches, one episode per lane, suspended episodes resumed)"
-            return self._rollout_scripted(env_seeds, policy_seeds, action_gen)
-        spec = self._fused_policy_spec()
-        if spec is not None and rng == "pcg64" and self.env_config.max_steps is not None and self.use_fused_rollout:
-            self._paths["rollout"] = "g2048_rollout (one persistent launch)"
-            return self._rollout_fused(env_seeds, policy_seeds, spec, use_greedy, record_probs)
-        dspec = self._deep_spec() if self.use_fused_policy else None
-        if dspec is not None and rng == "pcg64" and self.use_fused_rollout:
-            self._paths["rollout"] = "g2048_deep_rollout (persistent launches, suspended episodes resumed)"
-            return self._rollout_deep(env_seeds, policy_seeds, dspec, use_greedy, record_probs)
-        if spec is not None:
-            dspec = None
-        if self._sized and self.use_fused_sized_rollout and rng == "pcg64":
-            rspec = self._sized_spec()
-            if rspec is not None:
-                self._paths["rollout"] = "g2048_sized_rollout (persistent launches, suspended episodes resumed)"
-                return self._rollout_sized(env_seeds, policy_seeds, rspec, use_greedy, record_probs)
+            chosen = self._check_scripted(action_gen, rng, record_probs), action_gen
+        else:
+            spec = self._fused_policy_spec()
+            chosen = self._persistent_family(rng, spec)
+        if chosen is not None:
+            self._paths["rollout"] = self._PERSISTENT[chosen[0]].rollout_path
+            return self._play_persistent(*chosen, env_seeds, policy_seeds, use_greedy, rows=True,
+                                         record_probs=record_probs)
+        # step by step: the fused forward + choice of whichever policy kernel covers the net, else the GEMM path
+        dspec = self._deep_spec() if self.use_fused_policy and spec is None else None
         sspec = self._sized_spec() if self.use_fused_sized_policy else None
         self._paths["rollout"] = ("g2048_policy + g2048_step per step (active lanes)" if spec is not None else
                                   "g2048_deep_policy + g2048_step per step (active lanes)" if dspec is not None else
@@ -1398,17 +1373,13 @@ class ReinforceAgent:
                                   "hipBLASLt forward (active lanes) + g2048_sample + " +
                                   ("g2048_sized_step" if self._sized else "g2048_step") + " per step")
         env = self._vec_env(n, rng)
-        env.reset(seed=_seed_seq(env_seeds))
+        env.reset(seed=rollouts.seed_seq(env_seeds))
         dev = self.device
         from .vec_env import _as_u64_seeds
 
-        pseeds = _as_u64_seeds(_seed_seq(policy_seeds), n, 0, dev)
-        pst = torch.empty(2 * n, dtype=torch.int64, device=dev)
-        pinc = torch.empty(2 * n, dtype=torch.int64, device=dev)
-        pbuf = torch.empty(n, dtype=torch.int64, device=dev)
+        pseeds = _as_u64_seeds(rollouts.seed_seq(policy_seeds), n, 0, dev)
         rng_mode = L.RNG_PCG64 if rng == "pcg64" else L.RNG_PHILOX
-        if rng_mode == L.RNG_PCG64:
-            L.check(self._lib.g2048_seed_pcg64(L.ptr(pseeds), L.ptr(pst), L.ptr(pinc), L.ptr(pbuf), n, self._stream))
+        pst, pinc, pbuf = rollouts.pcg64_stream(self._lib, pseeds, self._stream, seeded=rng_mode == L.RNG_PCG64)
         ms = self.env_config.max_steps
         cap = int(ms) if (ms is not None and ms > 0) else 1024
         cap = max(cap, 1)
@@ -1493,356 +1464,82 @@ class ReinforceAgent:
                                max_tile=env.max_tile_seen.clone(), final_boards=env.board.clone(),
                                probs=probs[:T] if probs is not None else None)
 
-    def _rollout_fused(self, env_seeds, policy_seeds, spec, use_greedy: bool, record_probs: bool) -> TrajectoryBatch:
-        """rollout_batch in ONE launch (g2048_rollout): every episode runs to its end inside a persistent kernel
-        (fused policy + env step per step, episode slots refilled from a work queue)."""
-        from .config import env_cfg_struct
-        from .vec_env import _as_u64_seeds
+    # ------------------------------------------------------------------- persistent rollouts / evaluations
+    # Whole episodes inside persistent launches, driven by rollouts.run_growing (trajectory rows) and
+    # rollouts.run_budgeted (scores only).
+    _PERSISTENT = {
+        "fused": _Family("g2048_rollout", "g2048_rollout_eval",
+                         "g2048_rollout (one persistent launch)",
+                         "g2048_rollout_eval (one persistent launch, no trajectory rows)", None, None),
+        "deep": _Family("g2048_deep_rollout", "g2048_deep_eval",
+                        "g2048_deep_rollout (persistent launches, suspended episodes resumed)",
+                        "g2048_deep_eval (persistent launches, no trajectory rows, suspended episodes resumed)",
+                        "deep_rollout", None),
+        "sized": _Family("g2048_sized_rollout", "g2048_sized_eval",
+                         "g2048_sized_rollout (persistent launches, suspended episodes resumed)",
+                         "g2048_sized_eval (persistent launches, no trajectory rows, suspended episodes resumed)",
+                         "sized_rollout", "sized_rollout_max_workgroups", sized=True),
+        "scripted": _Family("g2048_scripted_rollout", "g2048_scripted_eval",
+                            "g2048_scripted_rollout (persistent launches, one episode per lane, suspended episodes "
+                            "resumed)",
+                            "g2048_scripted_eval (persistent launches, one episode per lane, no trajectory rows, "
+                            "suspended episodes resumed)",
+                            "scripted_rollout", "scripted_max_workgroups", scripted=True),
+        "sized_scripted": _Family("g2048_sized_scripted_rollout", "g2048_sized_scripted_eval",
+                                  "g2048_sized_scripted_rollout (persistent launches, one episode per lane, suspended "
+                                  "episodes resumed)",
+                                  "g2048_sized_scripted_eval (persistent launches, one episode per lane, no trajectory "
+                                  "rows, suspended episodes resumed)",
+                                  "scripted_rollout", "scripted_max_workgroups", sized=True, scripted=True),
+    }
 
-        n = len(env_seeds)
-        dev = self.device
-        es = _as_u64_seeds(_seed_seq(env_seeds), n, 0, dev)
-        ps = _as_u64_seeds(_seed_seq(policy_seeds), n, 0, dev)
-        streams = []
-        for seeds in (es, ps):
-            st = torch.empty(2 * n, dtype=torch.int64, device=dev)
-            inc = torch.empty(2 * n, dtype=torch.int64, device=dev)
-            buf = torch.empty(n, dtype=torch.int64, device=dev)
-            L.check(self._lib.g2048_seed_pcg64(L.ptr(seeds), L.ptr(st), L.ptr(inc), L.ptr(buf), n, self._stream))
-            streams += [st, inc, buf]
-        cap = max(int(self.env_config.max_steps), 1)
-        boards = torch.empty(cap, n, dtype=torch.int64, device=dev)
-        actions = torch.zeros(cap, n, dtype=torch.uint8, device=dev)
-        rewards = torch.zeros(cap, n, dtype=torch.float64, device=dev)
-        flags = torch.full((cap, n), L.F_INACTIVE, dtype=torch.uint8, device=dev)
-        probs = torch.zeros(cap, n, 4, dtype=torch.float32, device=dev) if record_probs else None
-        lengths = torch.empty(n, dtype=torch.int32, device=dev)
-        totals = torch.empty(n, dtype=torch.float64, device=dev)
-        max_e = torch.empty(n, dtype=torch.uint8, device=dev)
-        final = torch.empty(n, dtype=torch.int64, device=dev)
-        queue = torch.zeros(1, dtype=torch.int32, device=dev)
-        cfg = env_cfg_struct(self.env_config)
-        packed = self._packed_policy(spec)
-        L.check(self._lib.g2048_rollout(L.ptr(packed), spec[0], spec[1], spec[2], ctypes.byref(cfg), int(use_greedy),
-                                        *[L.ptr(t) for t in streams], L.ptr(queue), n, cap, L.ptr(boards),
-                                        L.ptr(actions), L.ptr(rewards), L.ptr(flags),
-                                        L.ptr(probs) if probs is not None else None, L.ptr(lengths), L.ptr(totals),
-                                        L.ptr(max_e), L.ptr(final), self._stream))
-        T = int(lengths.max().item()) if n else 0
-        return TrajectoryBatch(boards=boards[:T], actions=actions[:T], rewards=rewards[:T], flags=flags[:T],
-                               lengths=lengths, total_reward=totals,
-                               max_tile=torch.ones(n, dtype=torch.int64, device=dev) << max_e.to(torch.int64),
-                               final_boards=final, probs=probs[:T] if probs is not None else None)
-
-    # first trajectory capacity of g2048_deep_rollout when max_steps is None (doubled while episodes run past it), and
-    # the most rows it may grow to (an episode that never ends raises instead of exhausting device memory)
+    # g2048_deep_rollout (any depth, 4 x 4): its first trajectory capacity when max_steps is None (doubled while
+    # episodes run past it; a finite max_steps is the capacity, so that no episode is ever suspended), and the most rows
+    # it may grow to (an episode that never ends raises instead of exhausting device memory)
     deep_rollout_cap0 = 512
     deep_rollout_max_rows = 1 << 24
-
-    def _rollout_deep(self, env_seeds, policy_seeds, dspec, use_greedy: bool, record_probs: bool) -> TrajectoryBatch:
-        """rollout_batch through g2048_deep_rollout (any depth, one-hot obs, max_steps None): every episode runs
-        inside a persistent launch until it ends or fills the trajectory buffer's `cap` rows; the episodes that
-        filled it are suspended by the kernel, the buffer grows (x2) and one more launch resumes just those."""
-        from .config import env_cfg_struct
-        from .vec_env import _as_u64_seeds
-
-        n = len(env_seeds)
-        dev = self.device
-        es = _as_u64_seeds(_seed_seq(env_seeds), n, 0, dev)
-        ps = _as_u64_seeds(_seed_seq(policy_seeds), n, 0, dev)
-        streams = []
-        for seeds in (es, ps):
-            st = torch.empty(2 * n, dtype=torch.int64, device=dev)
-            inc = torch.empty(2 * n, dtype=torch.int64, device=dev)
-            buf = torch.empty(n, dtype=torch.int64, device=dev)
-            L.check(self._lib.g2048_seed_pcg64(L.ptr(seeds), L.ptr(st), L.ptr(inc), L.ptr(buf), n, self._stream))
-            streams += [st, inc, buf]
-        ms = self.env_config.max_steps
-        cap = max(int(ms) if ms is not None else self.deep_rollout_cap0, 1)
-        boards = torch.empty(cap, n, dtype=torch.int64, device=dev)
-        actions = torch.zeros(cap, n, dtype=torch.uint8, device=dev)
-        rewards = torch.zeros(cap, n, dtype=torch.float64, device=dev)
-        flags = torch.full((cap, n), L.F_INACTIVE, dtype=torch.uint8, device=dev)
-        probs = torch.zeros(cap, n, 4, dtype=torch.float32, device=dev) if record_probs else None
-        lengths = torch.empty(n, dtype=torch.int32, device=dev)
-        totals = torch.empty(n, dtype=torch.float64, device=dev)
-        max_e = torch.empty(n, dtype=torch.uint8, device=dev)
-        final = torch.empty(n, dtype=torch.int64, device=dev)
-        sus_board = torch.empty(n, dtype=torch.int64, device=dev)
-        sus_meta = torch.empty(3 * n, dtype=torch.int32, device=dev)
-        sus_total = torch.empty(n, dtype=torch.float64, device=dev)
-        sus_list = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
-        sus_count = torch.zeros(1, dtype=torch.int32, device=dev)
-        sus = L.Suspend(*[L.ptr(t) for t in (sus_board, sus_meta, sus_total, sus_list, sus_count)])
-        queue = torch.zeros(1, dtype=torch.int32, device=dev)
-        cfg = env_cfg_struct(self.env_config)
-        packed = self._pack_deep(self.params, dspec, "actor", 4)
-        obs_code, hidden, act, harr = dspec
-        order, n_order, resume = None, n, 0
-        while True:
-            traj = L.Traj(*[L.ptr(t) for t in (boards, actions, rewards, flags, probs, lengths, totals, max_e, final)])
-            L.check(self._lib.g2048_deep_rollout(L.ptr(packed), len(hidden), harr, act, ctypes.byref(cfg),
-                                                 int(use_greedy), *[L.ptr(t) for t in streams], L.ptr(queue),
-                                                 L.ptr(order), n_order, resume, ctypes.byref(sus), n, cap,
-                                                 ctypes.byref(traj), self._stream))
-            k = int(sus_count.item())          # one host sync per launch
-            if k == 0:
-                break
-            order, n_order, resume = sus_list[:k].clone(), k, 1
-            queue.zero_()
-            sus_count.zero_()
-            grow = cap
-            # The batch is time-major [T, n] for all n episodes (the update's layout), so a few long episodes grow
-            # every lane's rows.  An episode that never ends (max_steps None with invalid actions allowed, where the
-            # reference itself would loop forever) must not run the device out of memory: refuse past the rows the
-            # free memory holds, or past deep_rollout_max_rows.
-            row_bytes = n * (8 + 1 + 8 + 1 + (16 if probs is not None else 0))
-            free_b = 1 << 62
-            if dev.type == "cuda":
-                # free device memory plus what torch's caching allocator holds reserved but unused (torch.cat below
-                # reuses or releases that cache before it would fail)
-                free_b = (torch.cuda.mem_get_info(dev)[0] + torch.cuda.memory_reserved(dev) -
-                          torch.cuda.memory_allocated(dev))
-            if cap + grow > self.deep_rollout_max_rows or (cap + grow) * row_bytes > free_b + cap * row_bytes // 2:
-                hint = "set max_steps" + ("" if self.env_config.use_action_mask else " or use_action_mask=True")
-                raise RuntimeError(
-                    f"rollout_batch (max_steps=None): {k} episode(s) still running after {cap} steps; growing the "
-                    f"[T, n] trajectory buffer to {cap + grow} rows needs {(cap + grow) * row_bytes / 2**30:.1f} GiB "
-                    f"(free: {free_b / 2**30:.1f} GiB, row limit {self.deep_rollout_max_rows}) -- {hint}")
-            boards = torch.cat([boards, torch.empty(grow, n, dtype=torch.int64, device=dev)])
-            actions = torch.cat([actions, torch.zeros(grow, n, dtype=torch.uint8, device=dev)])
-            rewards = torch.cat([rewards, torch.zeros(grow, n, dtype=torch.float64, device=dev)])
-            flags = torch.cat([flags, torch.full((grow, n), L.F_INACTIVE, dtype=torch.uint8, device=dev)])
-            if probs is not None:
-                probs = torch.cat([probs, torch.zeros(grow, n, 4, dtype=torch.float32, device=dev)])
-            cap += grow
-        T = int(lengths.max().item()) if n else 0
-        return TrajectoryBatch(boards=boards[:T], actions=actions[:T], rewards=rewards[:T], flags=flags[:T],
-                               lengths=lengths, total_reward=totals,
-                               max_tile=torch.ones(n, dtype=torch.int64, device=dev) << max_e.to(torch.int64),
-                               final_boards=final, probs=probs[:T] if probs is not None else None)
-
-    # Board sizes other than 4: the whole rollout through g2048_sized_rollout (persistent launches, as _rollout_deep)
-    # when the net fits it (_sized_spec) and the streams are PCG64.  Off by default: the general path stays the
-    # product path.  A class attribute, so that it can be switched for agents somebody else constructs (the runner).
+    # Board sizes other than 4: the whole rollout through g2048_sized_rollout when the net fits it (_sized_spec) and the
+    # streams are PCG64.  Off by default: the general path stays the product path.  A class attribute, so that it can
+    # be switched for agents somebody else constructs (the runner).
     use_fused_sized_rollout = False
     # its grid cap (0: two workgroups per CU; g2048_sized_rollout's max_workgroups), its first trajectory capacity
     # (max_steps when that is fewer rows; doubled while episodes run past it) and the most rows it may grow to
-    # (deep_rollout_cap0 / deep_rollout_max_rows for these boards)
     sized_rollout_max_workgroups = 0
     sized_rollout_cap0 = 512
     sized_rollout_max_rows = 1 << 24
-
-    def _rollout_sized(self, env_seeds, policy_seeds, sspec, use_greedy: bool, record_probs: bool) -> TrajectoryBatch:
-        """_rollout_deep for board sizes other than 4 (g2048_sized_rollout): boards are [W, cap, n] planes, final and
-        suspended boards [W, n]; every other buffer, the suspend / grow / resume loop and the refusal are
-        _rollout_deep's.  The batch has the fields, shapes and dtypes of the per-step sized path's."""
-        from .config import env_cfg_struct
-        from .vec_env import _as_u64_seeds
-
-        n = len(env_seeds)
-        dev = self.device
-        W = int(self._lib.g2048_sized_words(self.size))
-        es = _as_u64_seeds(_seed_seq(env_seeds), n, 0, dev)
-        ps = _as_u64_seeds(_seed_seq(policy_seeds), n, 0, dev)
-        streams = []
-        for seeds in (es, ps):
-            st = torch.empty(2 * n, dtype=torch.int64, device=dev)
-            inc = torch.empty(2 * n, dtype=torch.int64, device=dev)
-            buf = torch.empty(n, dtype=torch.int64, device=dev)
-            L.check(self._lib.g2048_seed_pcg64(L.ptr(seeds), L.ptr(st), L.ptr(inc), L.ptr(buf), n, self._stream))
-            streams += [st, inc, buf]
-        ms = self.env_config.max_steps
-        # the first capacity: sized_rollout_cap0 rows, or max_steps when that is fewer (no episode is then suspended)
-        cap = max(min(int(ms), int(self.sized_rollout_cap0)) if ms is not None else int(self.sized_rollout_cap0), 1)
-        boards = torch.empty(W, cap, n, dtype=torch.int64, device=dev)
-        actions = torch.zeros(cap, n, dtype=torch.uint8, device=dev)
-        rewards = torch.zeros(cap, n, dtype=torch.float64, device=dev)
-        flags = torch.full((cap, n), L.F_INACTIVE, dtype=torch.uint8, device=dev)
-        probs = torch.zeros(cap, n, 4, dtype=torch.float32, device=dev) if record_probs else None
-        lengths = torch.empty(n, dtype=torch.int32, device=dev)
-        totals = torch.empty(n, dtype=torch.float64, device=dev)
-        max_e = torch.empty(n, dtype=torch.uint8, device=dev)
-        final = torch.empty(W, n, dtype=torch.int64, device=dev)
-        sus_board = torch.empty(W, n, dtype=torch.int64, device=dev)
-        sus_meta = torch.empty(3 * n, dtype=torch.int32, device=dev)
-        sus_total = torch.empty(n, dtype=torch.float64, device=dev)
-        sus_list = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
-        sus_count = torch.zeros(1, dtype=torch.int32, device=dev)
-        sus = L.Suspend(*[L.ptr(t) for t in (sus_board, sus_meta, sus_total, sus_list, sus_count)])
-        queue = torch.zeros(1, dtype=torch.int32, device=dev)
-        cfg = env_cfg_struct(self.env_config)
-        packed = self._pack_sized(self.params, sspec, "actor", 4)
-        _, hidden, act, harr = sspec
-        order, n_order, resume = None, n, 0
-        while True:
-            traj = L.Traj(*[L.ptr(t) for t in (boards, actions, rewards, flags, probs, lengths, totals, max_e, final)])
-            L.check(self._lib.g2048_sized_rollout(self.size, L.ptr(packed), len(hidden), harr, act, ctypes.byref(cfg),
-                                                  int(use_greedy), *[L.ptr(t) for t in streams], L.ptr(queue),
-                                                  L.ptr(order), n_order, resume, ctypes.byref(sus), n, cap,
-                                                  ctypes.byref(traj), cap * n, int(self.sized_rollout_max_workgroups),
-                                                  self._stream))
-            k = int(sus_count.item())          # one host sync per launch
-            if k == 0:
-                break
-            order, n_order, resume = sus_list[:k].clone(), k, 1
-            queue.zero_()
-            sus_count.zero_()
-            grow = cap if ms is None else max(min(cap, int(ms) - cap), 1)   # never past max_steps rows
-            # as _rollout_deep: an episode that never ends must not run the device out of memory
-            row_bytes = n * (8 * W + 1 + 8 + 1 + (16 if probs is not None else 0))
-            free_b = 1 << 62
-            if dev.type == "cuda":
-                free_b = (torch.cuda.mem_get_info(dev)[0] + torch.cuda.memory_reserved(dev) -
-                          torch.cuda.memory_allocated(dev))
-            if cap + grow > self.sized_rollout_max_rows or (cap + grow) * row_bytes > free_b + cap * row_bytes // 2:
-                hint = "set max_steps" + ("" if self.env_config.use_action_mask else " or use_action_mask=True")
-                raise RuntimeError(
-                    f"rollout_batch (max_steps=None): {k} episode(s) still running after {cap} steps; growing the "
-                    f"[T, n] trajectory buffer to {cap + grow} rows needs {(cap + grow) * row_bytes / 2**30:.1f} GiB "
-                    f"(free: {free_b / 2**30:.1f} GiB, row limit {self.sized_rollout_max_rows}) -- {hint}")
-            boards = torch.cat([boards, torch.empty(W, grow, n, dtype=torch.int64, device=dev)], dim=1)
-            actions = torch.cat([actions, torch.zeros(grow, n, dtype=torch.uint8, device=dev)])
-            rewards = torch.cat([rewards, torch.zeros(grow, n, dtype=torch.float64, device=dev)])
-            flags = torch.cat([flags, torch.full((grow, n), L.F_INACTIVE, dtype=torch.uint8, device=dev)])
-            if probs is not None:
-                probs = torch.cat([probs, torch.zeros(grow, n, 4, dtype=torch.float32, device=dev)])
-            cap += grow
-        T = int(lengths.max().item()) if n else 0
-        return TrajectoryBatch(boards=boards[:, :T], actions=actions[:T], rewards=rewards[:T], flags=flags[:T],
-                               lengths=lengths, total_reward=totals,
-                               max_tile=torch.ones(n, dtype=torch.int64, device=dev) << max_e.to(torch.int64),
-                               final_boards=final, probs=probs[:T] if probs is not None else None)
-
-    # Score-only evaluation (evaluate_batch): the steps a persistent launch of g2048_deep_eval / g2048_sized_eval may
-    # add to an episode before it suspends it (so every launch is bounded), and the step count past which a still
-    # running episode is refused (an episode that never ends -- max_steps None with invalid actions allowed, where the
-    # reference itself loops forever -- raises instead of being relaunched for ever).  Class attributes, so that they
-    # can be set for agents somebody else constructs.
+    # Score-only evaluation (evaluate_batch): the steps a persistent launch of a *_eval kernel may add to an episode
+    # before it suspends it (so every launch is bounded), and the step count past which a still running episode is
+    # refused (an episode that never ends -- max_steps None with invalid actions allowed, where the reference itself
+    # loops forever -- raises instead of being relaunched for ever).  Class attributes, as above.
     eval_step_budget = 4096
     eval_max_steps = 1 << 20
-
-    def evaluate_batch(self, env_seeds, policy_seeds, use_greedy: bool = True, rng: str = "pcg64",
-                       action_gen=None) -> EvalBatch:
-        """The episodes rollout_batch plays for these seeds under the same agent settings, keeping only what an
-        evaluation reads of them (lengths, total_reward, max_tile, final_boards): no trajectory rows, so memory is O(n)
-        whatever the episodes' lengths.  The family is chosen by rollout_batch's own tests in its order; what no
-        persistent kernel covers goes through rollout_batch itself.  last_paths()["eval"] names what ran.
-        action_gen: as rollout_batch's (g2048_scripted_eval)."""
-        n = len(env_seeds)
-        if len(policy_seeds) != n:
-            raise ValueError("env_seeds and policy_seeds must have the same length")
-        if action_gen is not None:
-            self._check_scripted(action_gen, rng, False)
-            name = "g2048_sized_scripted_eval" if self._sized else "g2048_scripted_eval"
-            self._paths["eval"] = name + (" (persistent launches, one episode per lane, no trajectory rows, suspended "
-                                          "episodes resumed)")
-            return self._evaluate_scripted(env_seeds, policy_seeds, action_gen)
-        spec = self._fused_policy_spec()
-        if spec is not None and rng == "pcg64" and self.env_config.max_steps is not None and self.use_fused_rollout:
-            self._paths["eval"] = "g2048_rollout_eval (one persistent launch, no trajectory rows)"
-            return self._evaluate_persistent(env_seeds, policy_seeds, "fused", spec, use_greedy)
-        dspec = self._deep_spec() if self.use_fused_policy else None
-        if dspec is not None and rng == "pcg64" and self.use_fused_rollout:
-            self._paths["eval"] = "g2048_deep_eval (persistent launches, no trajectory rows, suspended episodes resumed)"
-            return self._evaluate_persistent(env_seeds, policy_seeds, "deep", dspec, use_greedy)
-        if self._sized and self.use_fused_sized_rollout and rng == "pcg64":
-            rspec = self._sized_spec()
-            if rspec is not None:
-                self._paths["eval"] = ("g2048_sized_eval (persistent launches, no trajectory rows, suspended episodes "
-                                       "resumed)")
-                return self._evaluate_persistent(env_seeds, policy_seeds, "sized", rspec, use_greedy)
-        b = self.rollout_batch(env_seeds, policy_seeds, use_greedy=use_greedy, rng=rng)
-        self._paths["eval"] = "rollout_batch (trajectory rows materialised): " + self._paths["rollout"]
-        return EvalBatch(lengths=b.lengths, total_reward=b.total_reward, max_tile=b.max_tile,
-                         final_boards=b.final_boards)
-
-    def _evaluate_persistent(self, env_seeds, policy_seeds, family: str, spec, use_greedy: bool) -> EvalBatch:
-        """evaluate_batch through the score-only form of a persistent rollout kernel (family "fused": g2048_rollout_eval,
-        one launch bounded by max_steps; "deep" / "sized": g2048_deep_eval / g2048_sized_eval, relaunching the episodes
-        the kernel suspended every eval_step_budget steps).  Allocates per episode the two streams and their seeds, the
-        four outputs and the suspend state; nothing grows between launches."""
-        from .config import env_cfg_struct
-        from .vec_env import _as_u64_seeds
-
-        n = len(env_seeds)
-        dev = self.device
-        W = int(self._lib.g2048_sized_words(self.size)) if family == "sized" else 1
-        planes = (lambda: torch.empty(W, n, dtype=torch.int64, device=dev)) if family == "sized" else \
-                 (lambda: torch.empty(n, dtype=torch.int64, device=dev))
-        es = _as_u64_seeds(_seed_seq(env_seeds), n, 0, dev)
-        ps = _as_u64_seeds(_seed_seq(policy_seeds), n, 0, dev)
-        streams = []
-        for seeds in (es, ps):
-            st = torch.empty(2 * n, dtype=torch.int64, device=dev)
-            inc = torch.empty(2 * n, dtype=torch.int64, device=dev)
-            buf = torch.empty(n, dtype=torch.int64, device=dev)
-            L.check(self._lib.g2048_seed_pcg64(L.ptr(seeds), L.ptr(st), L.ptr(inc), L.ptr(buf), n, self._stream))
-            streams += [st, inc, buf]
-        lengths = torch.empty(n, dtype=torch.int32, device=dev)
-        totals = torch.empty(n, dtype=torch.float64, device=dev)
-        max_e = torch.empty(n, dtype=torch.uint8, device=dev)
-        final = planes()
-        out = L.EvalOut(*[L.ptr(t) for t in (lengths, totals, max_e, final)])
-        queue = torch.zeros(1, dtype=torch.int32, device=dev)
-        cfg = env_cfg_struct(self.env_config)
-        if family == "fused":
-            packed = self._packed_policy(spec)
-            L.check(self._lib.g2048_rollout_eval(L.ptr(packed), spec[0], spec[1], spec[2], ctypes.byref(cfg),
-                                                 int(use_greedy), *[L.ptr(t) for t in streams], L.ptr(queue), n,
-                                                 ctypes.byref(out), self._stream))
-        else:
-            sus_board = planes()
-            sus_meta = torch.empty(3 * n, dtype=torch.int32, device=dev)
-            sus_total = torch.empty(n, dtype=torch.float64, device=dev)
-            # two episode lists: the one a launch reads as its order and the one it fills with what it suspends
-            lists = [torch.empty(max(n, 1), dtype=torch.int32, device=dev) for _ in range(2)]
-            sus_count = torch.zeros(1, dtype=torch.int32, device=dev)
-            _, hidden, act, harr = spec
-            if family == "deep":
-                packed = self._pack_deep(self.params, spec, "actor", 4)
-            else:
-                packed = self._pack_sized(self.params, spec, "actor", 4)
-            budget = max(int(self.eval_step_budget), 1)
-            most = max(int(self.eval_max_steps), 1)
-            limit = min(budget, most)                   # no launch plays an episode past eval_max_steps
-            order, n_order, resume = None, n, 0
-            while True:
-                sus = L.Suspend(*[L.ptr(t) for t in (sus_board, sus_meta, sus_total, lists[0], sus_count)])
-                common = (len(hidden), harr, act, ctypes.byref(cfg), int(use_greedy), *[L.ptr(t) for t in streams],
-                          L.ptr(queue), L.ptr(order), n_order, resume, ctypes.byref(sus), n, limit, ctypes.byref(out))
-                if family == "deep":
-                    L.check(self._lib.g2048_deep_eval(L.ptr(packed), *common, self._stream))
-                else:
-                    L.check(self._lib.g2048_sized_eval(self.size, L.ptr(packed), *common,
-                                                       int(self.sized_rollout_max_workgroups), self._stream))
-                k = int(sus_count.item())          # one host sync per launch
-                if k == 0:
-                    break
-                if limit >= most:
-                    hint = "set max_steps" + ("" if self.env_config.use_action_mask else " or use_action_mask=True")
-                    raise RuntimeError(
-                        f"evaluate_batch: {k} episode(s) still running after {limit} steps; playing on would pass "
-                        f"eval_max_steps = {most} -- {hint}")
-                order, n_order, resume = lists[0], k, 1
-                lists.reverse()
-                queue.zero_()
-                sus_count.zero_()
-                limit = min(limit + budget, most)
-        return EvalBatch(lengths=lengths, total_reward=totals,
-                         max_tile=torch.ones(n, dtype=torch.int64, device=dev) << max_e.to(torch.int64),
-                         final_boards=final)
-
-    # Scripted play (rollout_batch / evaluate_batch with action_gen = PriorityPolicy / UniformPolicy; no net, so the
-    # use_fused_* switches do not apply): the grid cap of g2048_scripted_* (0: what n needs, at most what is resident),
-    # the first trajectory capacity (max_steps when that is fewer rows; doubled while episodes run past it) and the
-    # most rows it may grow to.  evaluate_batch uses eval_step_budget / eval_max_steps.  Class attributes, as above.
+    # Scripted play (action_gen = PriorityPolicy / UniformPolicy; no net, so the use_fused_* switches do not apply): the
+    # grid cap of g2048_scripted_* (0: what n needs, at most what is resident), the first trajectory capacity and the
+    # most rows, as the sized rollout's.  evaluate_batch uses eval_step_budget / eval_max_steps.
     scripted_max_workgroups = 0
     scripted_rollout_cap0 = 512
     scripted_rollout_max_rows = 1 << 24
 
-    def _check_scripted(self, action_gen, rng: str, record_probs: bool) -> None:
-        """The refusals of the batched scripted path, before any device call."""
+    def _persistent_family(self, rng: str, spec):
+        """("fused" | "deep" | "sized", spec) of the persistent kernel family that plays the net's episodes under
+        these settings, or None (the per-step path then runs): rollout_batch's choice, which evaluate_batch shares.
+        spec: the caller's _fused_policy_spec()."""
+        if rng != "pcg64":
+            return None
+        if self.use_fused_rollout:
+            if spec is not None and self.env_config.max_steps is not None:
+                return "fused", spec
+            dspec = self._deep_spec() if self.use_fused_policy else None
+            if dspec is not None:
+                return "deep", dspec
+        if self._sized and self.use_fused_sized_rollout:
+            rspec = self._sized_spec()
+            if rspec is not None:
+                return "sized", rspec
+        return None
+
+    def _check_scripted(self, action_gen, rng: str, record_probs: bool) -> str:
+        """The refusals of the batched scripted path, before any device call; returns its family."""
         from .policies import PriorityPolicy, UniformPolicy
 
         if not isinstance(action_gen, (PriorityPolicy, UniformPolicy)):
@@ -1857,144 +1554,98 @@ class ReinforceAgent:
         if isinstance(action_gen, PriorityPolicy) and not self.env_config.use_action_mask:
             raise ValueError("a PriorityPolicy needs env_config.use_action_mask=True on the batched path (its choice is "
                              "read off the action mask)")
+        return "sized_scripted" if self._sized else "scripted"
 
-    def _scripted_buffers(self, env_seeds, policy_seeds):
-        """The per-episode buffers both scripted host loops share: the two PCG64 streams, the four outputs and the
-        suspend state (board planes [W, n] for sizes other than 4)."""
-        from .vec_env import _as_u64_seeds
+    def _play_persistent(self, family: str, spec, env_seeds, policy_seeds, use_greedy: bool, rows: bool,
+                         record_probs: bool = False):
+        """Every episode inside persistent launches of `family` (spec: its net spec, or the scripted player):
+        rows=True records the trajectory (TrajectoryBatch; rollouts.run_growing), rows=False keeps the scores alone
+        (EvalBatch; rollouts.run_budgeted).  Builds the per-episode buffers and the family's one C call."""
+        from .config import env_cfg_struct
 
-        n = len(env_seeds)
-        dev = self.device
-        W = int(self._lib.g2048_sized_words(self.size)) if self._sized else 1
-        planes = (lambda: torch.empty(W, n, dtype=torch.int64, device=dev)) if self._sized else \
-                 (lambda: torch.empty(n, dtype=torch.int64, device=dev))
-        es = _as_u64_seeds(_seed_seq(env_seeds), n, 0, dev)
-        ps = _as_u64_seeds(_seed_seq(policy_seeds), n, 0, dev)
-        streams = []
-        for seeds in (es, ps):
-            st = torch.empty(2 * n, dtype=torch.int64, device=dev)
-            inc = torch.empty(2 * n, dtype=torch.int64, device=dev)
-            buf = torch.empty(n, dtype=torch.int64, device=dev)
-            L.check(self._lib.g2048_seed_pcg64(L.ptr(seeds), L.ptr(st), L.ptr(inc), L.ptr(buf), n, self._stream))
-            streams += [st, inc, buf]
-        lengths = torch.empty(n, dtype=torch.int32, device=dev)
-        totals = torch.empty(n, dtype=torch.float64, device=dev)
-        max_e = torch.empty(n, dtype=torch.uint8, device=dev)
-        final = planes()
-        sus_board = planes()
-        sus_meta = torch.empty(3 * n, dtype=torch.int32, device=dev)
-        sus_total = torch.empty(n, dtype=torch.float64, device=dev)
-        sus_count = torch.zeros(1, dtype=torch.int32, device=dev)
+        n, dev, lib = len(env_seeds), self.device, self._lib
+        fam = self._PERSISTENT[family]
+        fn = getattr(lib, fam.rollout if rows else fam.evaluate)
+        W = int(lib.g2048_sized_words(self.size)) if fam.sized else None
+        # the buffers, in the order the code before this driver made them; seeds: held, unused, until this call returns
+        streams, seeds = rollouts.episode_streams(lib, env_seeds, policy_seeds, dev, self._stream)
+        ms, max_rows, traj = self.env_config.max_steps, None, None
+        if rows:
+            # the first capacity: <tuning>_cap0 rows, or max_steps when that is fewer; g2048_rollout and
+            # g2048_deep_rollout take max_steps rows whenever it is finite, so that none of their episodes is suspended
+            if fam.tuning is not None:
+                first, max_rows = getattr(self, fam.tuning + "_cap0"), getattr(self, fam.tuning + "_max_rows")
+            if ms is not None:
+                first = ms if family in ("fused", "deep") else min(ms, first)
+            traj = rollouts.TrajectoryRows(n, dev, W, probs=record_probs, cap=max(int(first), 1))
+        outs = rollouts.EpisodeOutputs(n, dev, W)
+        # max_steps bounds g2048_rollout's episodes: it suspends none
+        sus = None if family == "fused" else rollouts.SuspendState(n, dev, W)
         queue = torch.zeros(1, dtype=torch.int32, device=dev)
-        return W, streams, (lengths, totals, max_e, final), (sus_board, sus_meta, sus_total), sus_count, queue
-
-    def _rollout_scripted(self, env_seeds, policy_seeds, policy) -> TrajectoryBatch:
-        """rollout_batch for a scripted player (g2048_scripted_rollout / g2048_sized_scripted_rollout): the suspend /
-        grow / resume loop and the refusal of _rollout_deep / _rollout_sized around a kernel that needs no net.  The
-        batch has the fields, shapes and dtypes of the net-driven paths' (probs None)."""
-        from .config import env_cfg_struct
-
-        n = len(env_seeds)
-        dev = self.device
-        sized = self._sized
-        W, streams, outs, sus_state, sus_count, queue = self._scripted_buffers(env_seeds, policy_seeds)
-        lengths, totals, max_e, final = outs
-        ms = self.env_config.max_steps
-        cap0 = int(self.scripted_rollout_cap0)
-        cap = max(min(int(ms), cap0) if ms is not None else cap0, 1)
-        bshape = (lambda rows: (W, rows, n)) if sized else (lambda rows: (rows, n))
-        boards = torch.empty(bshape(cap), dtype=torch.int64, device=dev)
-        actions = torch.zeros(cap, n, dtype=torch.uint8, device=dev)
-        rewards = torch.zeros(cap, n, dtype=torch.float64, device=dev)
-        flags = torch.full((cap, n), L.F_INACTIVE, dtype=torch.uint8, device=dev)
-        sus_list = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
-        sus = L.Suspend(*[L.ptr(t) for t in (*sus_state, sus_list, sus_count)])
         cfg = env_cfg_struct(self.env_config)
-        script = policy._script()
-        order, n_order, resume = None, n, 0
-        while True:
-            traj = L.Traj(*[L.ptr(t) for t in (boards, actions, rewards, flags, None, lengths, totals, max_e, final)])
-            common = (ctypes.byref(script), ctypes.byref(cfg), *[L.ptr(t) for t in streams], L.ptr(queue), L.ptr(order),
-                      n_order, resume, ctypes.byref(sus), n, cap, ctypes.byref(traj))
-            if sized:
-                L.check(self._lib.g2048_sized_scripted_rollout(self.size, *common, cap * n,
-                                                               int(self.scripted_max_workgroups), self._stream))
+        # the arguments before and after the part that changes from launch to launch
+        if fam.scripted:
+            script = spec._script()
+            head = (ctypes.byref(script), ctypes.byref(cfg))
+        elif family == "fused":
+            head = (L.ptr(self._packed_policy(spec)), *spec, ctypes.byref(cfg), int(use_greedy))
+        else:
+            _, hidden, act, harr = spec
+            packed = (self._pack_sized if fam.sized else self._pack_deep)(self.params, spec, "actor", 4)
+            head = (L.ptr(packed), len(hidden), harr, act, ctypes.byref(cfg), int(use_greedy))
+        head = ((self.size,) if fam.sized else ()) + head + tuple(L.ptr(t) for t in streams) + (L.ptr(queue),)
+        tail = (() if fam.grid_cap is None else (int(getattr(self, fam.grid_cap)),)) + (self._stream,)
+
+        def launch(order, n_order, resume, sus, limit):
+            # built per launch: the rows' pointers change when they grow, the suspend list with every resume
+            if sus is None:    # g2048_rollout: no order, nothing suspended, and the fields of Traj one by one
+                args = (n, limit, *traj.pointers(), *outs.pointers) if rows else (n, ctypes.byref(outs.eval_out()))
             else:
-                L.check(self._lib.g2048_scripted_rollout(*common, int(self.scripted_max_workgroups), self._stream))
-            k = int(sus_count.item())          # one host sync per launch
-            if k == 0:
-                break
-            order, n_order, resume = sus_list[:k].clone(), k, 1
-            queue.zero_()
-            sus_count.zero_()
-            grow = cap if ms is None else max(min(cap, int(ms) - cap), 1)   # never past max_steps rows
-            # as _rollout_deep: an episode that never ends must not run the device out of memory
-            row_bytes = n * (8 * W + 1 + 8 + 1)
-            free_b = 1 << 62
-            if dev.type == "cuda":
-                free_b = (torch.cuda.mem_get_info(dev)[0] + torch.cuda.memory_reserved(dev) -
-                          torch.cuda.memory_allocated(dev))
-            if cap + grow > self.scripted_rollout_max_rows or (cap + grow) * row_bytes > free_b + cap * row_bytes // 2:
-                hint = "set max_steps" + ("" if self.env_config.use_action_mask else " or use_action_mask=True")
-                raise RuntimeError(
-                    f"rollout_batch (max_steps=None): {k} episode(s) still running after {cap} steps; growing the "
-                    f"[T, n] trajectory buffer to {cap + grow} rows needs {(cap + grow) * row_bytes / 2**30:.1f} GiB "
-                    f"(free: {free_b / 2**30:.1f} GiB, row limit {self.scripted_rollout_max_rows}) -- {hint}")
-            boards = torch.cat([boards, torch.empty(bshape(grow), dtype=torch.int64, device=dev)], dim=1 if sized else 0)
-            actions = torch.cat([actions, torch.zeros(grow, n, dtype=torch.uint8, device=dev)])
-            rewards = torch.cat([rewards, torch.zeros(grow, n, dtype=torch.float64, device=dev)])
-            flags = torch.cat([flags, torch.full((grow, n), L.F_INACTIVE, dtype=torch.uint8, device=dev)])
-            cap += grow
-        T = int(lengths.max().item()) if n else 0
-        return TrajectoryBatch(boards=boards[:, :T] if sized else boards[:T], actions=actions[:T], rewards=rewards[:T],
-                               flags=flags[:T], lengths=lengths, total_reward=totals,
-                               max_tile=torch.ones(n, dtype=torch.int64, device=dev) << max_e.to(torch.int64),
-                               final_boards=final, probs=None)
+                out = traj.traj(outs) if rows else outs.eval_out()
+                args = (L.ptr(order), n_order, resume, ctypes.byref(sus.struct()), n, limit, ctypes.byref(out))
+                if fam.sized and rows:
+                    args += (traj.plane_stride,)
+            L.check(fn(*head, *args, *tail))
 
-    def _evaluate_scripted(self, env_seeds, policy_seeds, policy) -> EvalBatch:
-        """evaluate_batch for a scripted player (g2048_scripted_eval / g2048_sized_scripted_eval): _evaluate_persistent's
-        loop -- relaunch what the kernel suspended every eval_step_budget steps, two episode lists, refuse past
-        eval_max_steps; nothing grows between launches."""
-        from .config import env_cfg_struct
 
-        n = len(env_seeds)
+        hint = "set max_steps" + ("" if self.env_config.use_action_mask else " or use_action_mask=True")
+        if not rows:
+            rollouts.run_budgeted(launch, sus, queue, n, max(int(self.eval_step_budget), 1),
+                                  max(int(self.eval_max_steps), 1), hint)
+            return EvalBatch(lengths=outs.lengths, total_reward=outs.totals, max_tile=outs.max_tile,
+                             final_boards=outs.final)
+        T = rollouts.run_growing(launch, traj, outs, sus, queue, n, ms, max_rows, self._free_bytes, hint)
+        return TrajectoryBatch(**traj.sliced(T), lengths=outs.lengths, total_reward=outs.totals,
+                               max_tile=outs.max_tile, final_boards=outs.final)
+
+    def _free_bytes(self) -> int:
+        """Free device memory plus what torch's caching allocator holds reserved but unused."""
         dev = self.device
-        _, streams, outs, sus_state, sus_count, queue = self._scripted_buffers(env_seeds, policy_seeds)
-        lengths, totals, max_e, final = outs
-        out = L.EvalOut(*[L.ptr(t) for t in outs])
-        # two episode lists: the one a launch reads as its order and the one it fills with what it suspends
-        lists = [torch.empty(max(n, 1), dtype=torch.int32, device=dev) for _ in range(2)]
-        cfg = env_cfg_struct(self.env_config)
-        script = policy._script()
-        budget = max(int(self.eval_step_budget), 1)
-        most = max(int(self.eval_max_steps), 1)
-        limit = min(budget, most)                   # no launch plays an episode past eval_max_steps
-        order, n_order, resume = None, n, 0
-        while True:
-            sus = L.Suspend(*[L.ptr(t) for t in (*sus_state, lists[0], sus_count)])
-            common = (ctypes.byref(script), ctypes.byref(cfg), *[L.ptr(t) for t in streams], L.ptr(queue), L.ptr(order),
-                      n_order, resume, ctypes.byref(sus), n, limit, ctypes.byref(out),
-                      int(self.scripted_max_workgroups), self._stream)
-            if self._sized:
-                L.check(self._lib.g2048_sized_scripted_eval(self.size, *common))
-            else:
-                L.check(self._lib.g2048_scripted_eval(*common))
-            k = int(sus_count.item())          # one host sync per launch
-            if k == 0:
-                break
-            if limit >= most:
-                hint = "set max_steps" + ("" if self.env_config.use_action_mask else " or use_action_mask=True")
-                raise RuntimeError(
-                    f"evaluate_batch: {k} episode(s) still running after {limit} steps; playing on would pass "
-                    f"eval_max_steps = {most} -- {hint}")
-            order, n_order, resume = lists[0], k, 1
-            lists.reverse()
-            queue.zero_()
-            sus_count.zero_()
-            limit = min(limit + budget, most)
-        return EvalBatch(lengths=lengths, total_reward=totals,
-                         max_tile=torch.ones(n, dtype=torch.int64, device=dev) << max_e.to(torch.int64),
-                         final_boards=final)
+        if dev.type != "cuda":
+            return 1 << 62
+        return torch.cuda.mem_get_info(dev)[0] + torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev)
+
+    def evaluate_batch(self, env_seeds, policy_seeds, use_greedy: bool = True, rng: str = "pcg64",
+                       action_gen=None) -> EvalBatch:
+        """The episodes rollout_batch plays for these seeds under the same agent settings, keeping only what an
+        evaluation reads of them (lengths, total_reward, max_tile, final_boards): no trajectory rows, so memory is O(n)
+        whatever the episodes' lengths.  The family is rollout_batch's (_persistent_family); what no persistent kernel
+        covers goes through rollout_batch itself.  last_paths()["eval"] names what ran.
+        action_gen: as rollout_batch's (g2048_scripted_eval)."""
+        n = len(env_seeds)
+        if len(policy_seeds) != n:
+            raise ValueError("env_seeds and policy_seeds must have the same length")
+        if action_gen is not None:
+            chosen = self._check_scripted(action_gen, rng, False), action_gen
+        else:
+            chosen = self._persistent_family(rng, self._fused_policy_spec())
+        if chosen is not None:
+            self._paths["eval"] = self._PERSISTENT[chosen[0]].eval_path
+            return self._play_persistent(*chosen, env_seeds, policy_seeds, use_greedy, rows=False)
+        b = self.rollout_batch(env_seeds, policy_seeds, use_greedy=use_greedy, rng=rng)
+        self._paths["eval"] = "rollout_batch (trajectory rows materialised): " + self._paths["rollout"]
+        return EvalBatch(lengths=b.lengths, total_reward=b.total_reward, max_tile=b.max_tile,
+                         final_boards=b.final_boards)
 
     def trajectories_from_batch(self, batch: TrajectoryBatch, with_states: bool = True) -> list[dict[str, Any]]:
         """Convert a device batch to the reference's trajectory dicts (src/reinforce_agent.py:240-247)."""

@@ -333,7 +333,7 @@ def test_deep_rollout_suspend_resume_equals_stepwise(env, hidden):
     times as the buffer doubles) == the per-step path (g2048_deep_policy + g2048_step) on the same seeds: every board,
     action, fp64 reward, flag, probability, length, total, max tile and final board; sampled episodes replayed in the
     oracle (env + numpy Generator.choice on the recorded probabilities).
-    The third case (max_steps = 70) is NOT suspended: _rollout_deep takes cap = max_steps when that is finite, so
+    The third case (max_steps = 70) is NOT suspended: the deep family's first cap is max_steps when that is finite, so
     deep_rollout_cap0 has no effect and the case only compares the unsuspended 4-layer Sigmoid one-hot rollout with
     the per-step path.  Suspension under a finite max_steps (truncation from a restored step count) is reached through
     the score-only kernel in tests/test_gpu_rollout_replay.py::test_score_only_under_the_same_terms."""
