@@ -443,4 +443,8 @@ int g2048_onehot_dw1(const uint64_t* boards, const float* d1, int h1, int64_t m,
  * 17, part of this interface */
 #include "g2048_scripted.h"
 
+/* whole episodes and single choices of the expectimax search player: additive entry points of ABI 17, part of this
+ * interface */
+#include "g2048_search.h"
+
 #endif /* G2048_H */

@@ -29,7 +29,10 @@ SOURCES = [SRC, os.path.join(PKG_DIR, "csrc", "g2048_policy.hip"), os.path.join(
            os.path.join(PKG_DIR, "csrc", "g2048_sized_eval.hip"),
            # whole episodes of a scripted player (no net): 4 x 4 and sizes 2..8
            os.path.join(PKG_DIR, "csrc", "g2048_scripted.hip"),
-           os.path.join(PKG_DIR, "csrc", "g2048_sized_scripted.hip")]
+           os.path.join(PKG_DIR, "csrc", "g2048_sized_scripted.hip"),
+           # whole episodes and single choices of the expectimax search player: 4 x 4 and sizes 2..8
+           os.path.join(PKG_DIR, "csrc", "g2048_search.hip"),
+           os.path.join(PKG_DIR, "csrc", "g2048_sized_search.hip")]
 INCLUDE = os.path.join(REPO_ROOT, "include")
 ABI_VERSION = 17
 DEEP_MAX_HIDDEN = 4
@@ -47,6 +50,8 @@ G2048_OK, G2048_EINVAL, G2048_EHIP, G2048_ENOINIT = 0, 1, 2, 3
 # include/g2048_scripted.h
 SCRIPT_PRIORITY, SCRIPT_UNIFORM = 0, 1
 SCRIPT_BLOCK = 256
+# include/g2048_search.h
+SEARCH_MAX_DEPTH, SEARCH_MAX_WEIGHT = 2, 4096
 
 
 CSRC = os.path.join(PKG_DIR, "csrc")
@@ -80,7 +85,8 @@ def _object_for(src: str, flags: list[str]) -> str:
     h.update(_compiler_id().encode())
     hdrs = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".inc")))
     for f in [src] + hdrs + [os.path.join(INCLUDE, "g2048.h"), os.path.join(INCLUDE, "g2048_sized.h"),
-                                os.path.join(INCLUDE, "g2048_eval.h"), os.path.join(INCLUDE, "g2048_scripted.h")]:
+                                os.path.join(INCLUDE, "g2048_eval.h"), os.path.join(INCLUDE, "g2048_scripted.h"),
+                                os.path.join(INCLUDE, "g2048_search.h")]:
         with open(f, "rb") as fh:
             h.update(fh.read())
     return os.path.join(BUILD_DIR, f"{os.path.splitext(os.path.basename(src))[0]}-{h.hexdigest()[:16]}.o")
@@ -172,6 +178,12 @@ class EvalOut(ctypes.Structure):
 class Script(ctypes.Structure):
     """g2048_script: the scripted player of a launch (kind SCRIPT_*; order: PRIORITY's permutation of 0..3)."""
     _fields_ = [("kind", ctypes.c_int32), ("order", ctypes.c_uint8 * 4)]
+
+
+class Search(ctypes.Structure):
+    """g2048_search: the expectimax player of a launch (depth 0..2, four weights 0..4096)."""
+    _fields_ = [("depth", ctypes.c_int32), ("w_merge", ctypes.c_uint32), ("w_empty", ctypes.c_uint32),
+                ("w_smooth", ctypes.c_uint32), ("w_corner", ctypes.c_uint32)]
 
 
 _lib = None
@@ -268,7 +280,13 @@ def _declare(L):
                                                P(Suspend), i64, i64, P(Traj), i64, i32, vp]
     L.g2048_sized_scripted_eval.argtypes = [i32, P(Script), P(EnvCfg), vp, vp, vp, vp, vp, vp, vp, vp, i64, i32,
                                             P(Suspend), i64, i64, P(EvalOut), i32, vp]
-    for name in SIZED_SYMBOLS + EVAL_SYMBOLS + SCRIPTED_SYMBOLS:
+    L.g2048_search_rollout.argtypes = [P(Search)] + L.g2048_scripted_rollout.argtypes[1:]
+    L.g2048_search_eval.argtypes = [P(Search)] + L.g2048_scripted_eval.argtypes[1:]
+    L.g2048_sized_search_rollout.argtypes = [i32, P(Search)] + L.g2048_sized_scripted_rollout.argtypes[2:]
+    L.g2048_sized_search_eval.argtypes = [i32, P(Search)] + L.g2048_sized_scripted_eval.argtypes[2:]
+    L.g2048_search_choose.argtypes = [P(Search), vp, i64, vp, vp, vp]
+    L.g2048_sized_search_choose.argtypes = [i32, P(Search), vp, i64, vp, vp, vp]
+    for name in SIZED_SYMBOLS + EVAL_SYMBOLS + SCRIPTED_SYMBOLS + SEARCH_SYMBOLS:
         getattr(L, name).restype = ctypes.c_int
     for name in ("g2048_init", "g2048_seed_pcg64", "g2048_reset", "g2048_step", "g2048_obs", "g2048_move",
                  "g2048_sample", "g2048_returns", "g2048_symmetries", "g2048_policy_pack", "g2048_policy",
@@ -303,6 +321,10 @@ EVAL_SYMBOLS = ("g2048_rollout_eval", "g2048_deep_eval")
 # include/g2048_scripted.h (included by g2048.h): whole episodes of a scripted player
 SCRIPTED_SYMBOLS = ("g2048_scripted_rollout", "g2048_scripted_eval", "g2048_sized_scripted_rollout",
                     "g2048_sized_scripted_eval")
+
+# include/g2048_search.h (included by g2048.h): whole episodes and single choices of the expectimax search player
+SEARCH_SYMBOLS = ("g2048_search_rollout", "g2048_search_eval", "g2048_sized_search_rollout", "g2048_sized_search_eval",
+                  "g2048_search_choose", "g2048_sized_search_choose")
 
 
 def lib():

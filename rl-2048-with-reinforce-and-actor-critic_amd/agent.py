@@ -57,6 +57,8 @@ class _Family(NamedTuple):
     grid_cap: str | None    # the agent attribute holding the grid cap; None: the entry points take none
     sized: bool = False     # board sizes other than 4: size argument, [W, ...] board planes, a plane stride
     scripted: bool = False  # played by a PriorityPolicy / UniformPolicy instead of a net
+    search: bool = False    # played by an ExpectimaxPolicy instead of a net
+    budget: str = "eval_step_budget"   # the agent attribute holding evaluate_batch's steps per launch
 
 
 @dataclass
@@ -1349,9 +1351,9 @@ class ReinforceAgent:
         """Play one episode per lane (env.reset(seed=env_seeds[i]), policy stream default_rng(policy_seeds[i]))
         until every lane terminates or truncates -- the batched equivalent of calling run_episode for each
         (env_seed, policy_seed) pair (runner.py:587-591).  Everything stays on the device.
-        action_gen: a PriorityPolicy / UniformPolicy plays the episodes instead of the net (run_episode's action_gen,
-        batched: g2048_scripted_rollout); use_greedy is then ignored, as the reference ignores it when action_fn
-        answers."""
+        action_gen: a PriorityPolicy / UniformPolicy / ExpectimaxPolicy plays the episodes instead of the net
+        (run_episode's action_gen, batched: g2048_scripted_rollout / g2048_search_rollout); use_greedy is then ignored,
+        as the reference ignores it when action_fn answers."""
         n = len(env_seeds)
         if len(policy_seeds) != n:
             raise ValueError("env_seeds and policy_seeds must have the same length")
@@ -1491,6 +1493,19 @@ class ReinforceAgent:
                                   "g2048_sized_scripted_eval (persistent launches, one episode per lane, no trajectory "
                                   "rows, suspended episodes resumed)",
                                   "scripted_rollout", "scripted_max_workgroups", sized=True, scripted=True),
+        "search": _Family("g2048_search_rollout", "g2048_search_eval",
+                          "g2048_search_rollout (persistent launches, one episode and one expectimax per lane, "
+                          "suspended episodes resumed)",
+                          "g2048_search_eval (persistent launches, one episode and one expectimax per lane, no "
+                          "trajectory rows, suspended episodes resumed)",
+                          "search_rollout", "search_max_workgroups", search=True, budget="search_step_budget"),
+        "sized_search": _Family("g2048_sized_search_rollout", "g2048_sized_search_eval",
+                                "g2048_sized_search_rollout (persistent launches, one episode and one expectimax per "
+                                "lane, suspended episodes resumed)",
+                                "g2048_sized_search_eval (persistent launches, one episode and one expectimax per "
+                                "lane, no trajectory rows, suspended episodes resumed)",
+                                "search_rollout", "search_max_workgroups", sized=True, search=True,
+                                budget="search_step_budget"),
     }
 
     # g2048_deep_rollout (any depth, 4 x 4): its first trajectory capacity when max_steps is None (doubled while
@@ -1519,6 +1534,13 @@ class ReinforceAgent:
     scripted_max_workgroups = 0
     scripted_rollout_cap0 = 512
     scripted_rollout_max_rows = 1 << 24
+    # Search play (action_gen = ExpectimaxPolicy): the same three, and evaluate_batch's steps per launch, of their own
+    # and smaller -- a depth-2 step is thousands of moves, and a persistent launch on a shared machine must stay short.
+    # Estimates, not measurements: chosen so that a launch is a few hundred search steps per lane.
+    search_max_workgroups = 0
+    search_rollout_cap0 = 256
+    search_rollout_max_rows = 1 << 24
+    search_step_budget = 256
 
     def _persistent_family(self, rng: str, spec):
         """("fused" | "deep" | "sized", spec) of the persistent kernel family that plays the net's episodes under
@@ -1540,11 +1562,11 @@ class ReinforceAgent:
 
     def _check_scripted(self, action_gen, rng: str, record_probs: bool) -> str:
         """The refusals of the batched scripted path, before any device call; returns its family."""
-        from .policies import PriorityPolicy, UniformPolicy
+        from .policies import ExpectimaxPolicy, PriorityPolicy, UniformPolicy
 
-        if not isinstance(action_gen, (PriorityPolicy, UniformPolicy)):
+        if not isinstance(action_gen, (PriorityPolicy, UniformPolicy, ExpectimaxPolicy)):
             raise TypeError(
-                f"action_gen must be a PriorityPolicy or a UniformPolicy on the batched path (got "
+                f"action_gen must be a PriorityPolicy, a UniformPolicy or an ExpectimaxPolicy on the batched path (got "
                 f"{type(action_gen).__name__}); run_episode(env_seed, policy_seed, action_gen=...) is the host path "
                 f"for arbitrary callables")
         if rng != "pcg64":
@@ -1554,6 +1576,8 @@ class ReinforceAgent:
         if isinstance(action_gen, PriorityPolicy) and not self.env_config.use_action_mask:
             raise ValueError("a PriorityPolicy needs env_config.use_action_mask=True on the batched path (its choice is "
                              "read off the action mask)")
+        if isinstance(action_gen, ExpectimaxPolicy):     # computes validity itself: mask on or off
+            return "sized_search" if self._sized else "search"
         return "sized_scripted" if self._sized else "scripted"
 
     def _play_persistent(self, family: str, spec, env_seeds, policy_seeds, use_greedy: bool, rows: bool,
@@ -1584,8 +1608,8 @@ class ReinforceAgent:
         queue = torch.zeros(1, dtype=torch.int32, device=dev)
         cfg = env_cfg_struct(self.env_config)
         # the arguments before and after the part that changes from launch to launch
-        if fam.scripted:
-            script = spec._script()
+        if fam.scripted or fam.search:
+            script = spec._search() if fam.search else spec._script()
             head = (ctypes.byref(script), ctypes.byref(cfg))
         elif family == "fused":
             head = (L.ptr(self._packed_policy(spec)), *spec, ctypes.byref(cfg), int(use_greedy))
@@ -1610,7 +1634,7 @@ class ReinforceAgent:
 
         hint = "set max_steps" + ("" if self.env_config.use_action_mask else " or use_action_mask=True")
         if not rows:
-            rollouts.run_budgeted(launch, sus, queue, n, max(int(self.eval_step_budget), 1),
+            rollouts.run_budgeted(launch, sus, queue, n, max(int(getattr(self, fam.budget)), 1),
                                   max(int(self.eval_max_steps), 1), hint)
             return EvalBatch(lengths=outs.lengths, total_reward=outs.totals, max_tile=outs.max_tile,
                              final_boards=outs.final)
@@ -1631,7 +1655,8 @@ class ReinforceAgent:
         evaluation reads of them (lengths, total_reward, max_tile, final_boards): no trajectory rows, so memory is O(n)
         whatever the episodes' lengths.  The family is rollout_batch's (_persistent_family); what no persistent kernel
         covers goes through rollout_batch itself.  last_paths()["eval"] names what ran.
-        action_gen: as rollout_batch's (g2048_scripted_eval)."""
+        action_gen: as rollout_batch's (g2048_scripted_eval / g2048_search_eval, the latter search_step_budget steps
+        per launch)."""
         n = len(env_seeds)
         if len(policy_seeds) != n:
             raise ValueError("env_seeds and policy_seeds must have the same length")
@@ -1646,6 +1671,38 @@ class ReinforceAgent:
         self._paths["eval"] = "rollout_batch (trajectory rows materialised): " + self._paths["rollout"]
         return EvalBatch(lengths=b.lengths, total_reward=b.total_reward, max_tile=b.max_tile,
                          final_boards=b.final_boards)
+
+    @torch.no_grad()
+    def search_actions(self, boards: torch.Tensor, policy) -> tuple[torch.Tensor, torch.Tensor]:
+        """The ExpectimaxPolicy's choice on arbitrary boards (g2048_search_choose / g2048_sized_search_choose): the
+        teacher's move on states the net visited.  boards: int64, [...] bitboards at 4 x 4 or [W, ...] planes
+        otherwise -- TrajectoryBatch.boards as it is (rows past an episode's end are labelled like any board).
+        Returns (actions uint8 [...], q int64 [..., 4]): q[..., a] = Q_depth(board, a), -1 for an invalid action; a
+        board with no valid action gets action 0."""
+        from .policies import ExpectimaxPolicy
+
+        if not isinstance(policy, ExpectimaxPolicy):
+            raise TypeError(f"search_actions labels boards with an ExpectimaxPolicy (got {type(policy).__name__})")
+        if not isinstance(boards, torch.Tensor) or boards.dtype != torch.int64:
+            raise ValueError("boards must be an int64 tensor")
+        if self._sized:
+            W = int(self._lib.g2048_sized_words(self.size))
+            if boards.dim() < 1 or boards.shape[0] != W:
+                raise ValueError(f"boards of size {self.size} are [{W}, ...] planes (got shape {tuple(boards.shape)})")
+            shape = tuple(boards.shape[1:])
+        else:
+            shape = tuple(boards.shape)
+        flat = boards.to(self.device).reshape((W, -1) if self._sized else (-1,)).contiguous()
+        m = flat.shape[-1]
+        actions = torch.empty(m, dtype=torch.uint8, device=self.device)
+        q = torch.empty(m, 4, dtype=torch.int64, device=self.device)
+        sp = policy._search()
+        head = (self.size, ctypes.byref(sp)) if self._sized else (ctypes.byref(sp),)
+        fn = self._lib.g2048_sized_search_choose if self._sized else self._lib.g2048_search_choose
+        L.check(fn(*head, L.ptr(flat), m, L.ptr(actions), L.ptr(q), self._stream))
+        self._paths["search_actions"] = ("g2048_sized_search_choose" if self._sized else "g2048_search_choose") + \
+                                        " (one board per thread)"
+        return actions.view(shape), q.view(shape + (4,))
 
     def trajectories_from_batch(self, batch: TrajectoryBatch, with_states: bool = True) -> list[dict[str, Any]]:
         """Convert a device batch to the reference's trajectory dicts (src/reinforce_agent.py:240-247)."""
@@ -1689,15 +1746,15 @@ class ReinforceAgent:
                     use_greedy: bool = False) -> dict[str, Any]:
         """src/reinforce_agent.py:195-252.  Without action_gen the episode runs on the device lane path (same
         spawn and policy streams as the reference); with action_gen it steps the drop-in env from the host -- except
-        for a UniformPolicy, or a PriorityPolicy on an env with an action mask, which the device plays
-        (rollout_batch's action_gen).  A PriorityPolicy on a mask-less env is a plain callable here: it fails on the
+        for a UniformPolicy, an ExpectimaxPolicy, or a PriorityPolicy on an env with an action mask, which the device
+        plays (rollout_batch's action_gen).  A PriorityPolicy on a mask-less env is a plain callable here: it fails on the
         None mask and select_action falls back to the net, as the reference does."""
         if action_gen is None:
             return self.trajectories_from_batch(self.rollout_batch([env_seed], [policy_seed], use_greedy))[0]
-        from .policies import PriorityPolicy, UniformPolicy
+        from .policies import ExpectimaxPolicy, PriorityPolicy, UniformPolicy
 
-        if isinstance(action_gen, UniformPolicy) or (isinstance(action_gen, PriorityPolicy) and
-                                                     self.env_config.use_action_mask):
+        if isinstance(action_gen, (UniformPolicy, ExpectimaxPolicy)) or (isinstance(action_gen, PriorityPolicy) and
+                                                                         self.env_config.use_action_mask):
             return self.trajectories_from_batch(
                 self.rollout_batch([env_seed], [policy_seed], action_gen=action_gen))[0]
         from .env import Game2048Env

@@ -72,7 +72,8 @@ G2048_HD uint32_t uniform_choice(uint32_t mask_bits, bool has_mask, double u, fl
 
 // ---------------------------------------------------------------------------------------------------------------
 // The two games behind one interface: kWords board words, fresh (Game2048.reset: two spawns on the env stream), mask
-// (bit a = action a changes the board) and step (one Game2048Env.step; sc = the step count before it).
+// (bit a = action a changes the board), step (one Game2048Env.step; sc = the step count before it), and the two pieces
+// of a step a lookahead needs on their own: move and put.
 // ---------------------------------------------------------------------------------------------------------------
 
 // 4 x 4: the bitboard of g2048_core.h.  The move is board_move_alu -- no row table, so no LDS and no g2048_init --
@@ -98,6 +99,15 @@ struct Game4 {
                 (invalid ? kFInvalid : 0u) | (s.overflow ? kFOverflow : 0u);
         bw[0] = m;
     }
+    // the slide / merge alone (no spawn): out = move(bw, a), sum_e = the log2 sum of the merged tiles; true iff the
+    // board changed.  put: exponent e into the empty cell `cell`.  (The search player, g2048_search_core.h.)
+    G2048_HDM bool move(const uint64_t (&bw)[1], uint32_t a, uint64_t (&out)[1], uint32_t& sum_e) {
+        MoveSummary s;
+        out[0] = board_move_alu<false>(bw[0], a, s);
+        sum_e = s.sum_e;
+        return out[0] != bw[0];
+    }
+    G2048_HDM void put(uint64_t (&bw)[1], uint32_t cell, uint32_t e) { bw[0] |= (uint64_t)e << (4u * cell); }
 };
 
 // N x N, 2 <= N <= 8: the word planes of g2048_sized_core.h
@@ -129,6 +139,24 @@ struct GameN {
         for (int w = 0; w < kWords; w++) bw[w] = o.board.w[w];
         reward = o.reward;
         flags = o.flags;
+    }
+    // as Game4's
+    G2048_HDM bool move(const uint64_t (&bw)[kWords], uint32_t a, uint64_t (&out)[kWords], uint32_t& sum_e) {
+        MoveSummary s;
+        const sized::Board<N> m = sized::board_move<N, false>(load(bw), a, s, nullptr);
+        bool changed = false;
+#pragma unroll
+        for (int w = 0; w < kWords; w++) {
+            out[w] = m.w[w];
+            changed = changed || m.w[w] != bw[w];
+        }
+        sum_e = s.sum_e;
+        return changed;
+    }
+    G2048_HDM void put(uint64_t (&bw)[kWords], uint32_t cell, uint32_t e) {
+        const uint32_t word = cell >> 4, sh = 4u * (cell & 15u);
+#pragma unroll
+        for (int w = 0; w < kWords; w++) bw[w] |= word == (uint32_t)w ? (uint64_t)e << sh : 0ull;
     }
 };
 

@@ -89,14 +89,28 @@ __device__ __forceinline__ const ScriptArgs& args_per_lane() {
     return *(const ScriptArgs*)p;
 }
 
+// The player of scripted_kernel: the script of the launch.  A player of play_episodes says whether it draws from the
+// episode's policy stream (kernel-uniform: loaded at the claim and stored at a suspension only then) and plays one
+// step of an episode (episode_step's contract).
+template <class G>
+struct ScriptPlayer {
+    const ScriptArgs& a;
+    __device__ __forceinline__ bool policy_stream() const { return a.script.kind == scripted::kUniform; }
+    __device__ __forceinline__ bool step(scripted::Episode<G>& e, scripted::Row<G>& row) const {
+        return scripted::episode_step<G>(e, a.script, a.rc, a.max_steps, a.use_mask != 0, row);
+    }
+};
+
+// The persistent loop of every one-episode-per-lane kernel (scripted_kernel here, search_kernel of
+// g2048_search_kernel.h): claim / refill, resume, one step of the player, the row, end / suspend / keep.
 // G: scripted::Game4 or scripted::GameN<N>.  TRAJ = false is the score-only form: the same code without the
-// trajectory row; the episode's end and the suspension at `cap` steps are unchanged.  The script's kind is
-// kernel-uniform.  Under PRIORITY the policy stream is neither read nor written.
-template <class G, bool TRAJ>
-__global__ void __launch_bounds__(kScriptBlock) scripted_kernel(ScriptArgs a) {
+// trajectory row; the episode's end and the suspension at `cap` steps are unchanged.  The kernel's ScriptArgs are at
+// offset 0 of its kernarg segment (args_per_lane).
+template <class G, bool TRAJ, class Player>
+__device__ __forceinline__ void play_episodes(const Player& player) {
     constexpr int W = G::kWords;
     const int lane = (int)(threadIdx.x & 63);
-    const bool uniform = a.script.kind == scripted::kUniform;
+    const bool uniform = player.policy_stream();
     uint32_t ep = kNoEpisode;
     scripted::Episode<G> e{};
     bool drained = false;                              // wave-uniform: the queue is empty (claims only grow)
@@ -134,7 +148,7 @@ __global__ void __launch_bounds__(kScriptBlock) scripted_kernel(ScriptArgs a) {
         if (ep != kNoEpisode) {
             scripted::Row<G> row;
             const uint32_t t0 = e.t;
-            const bool ended = scripted::episode_step<G>(e, a.script, a.rc, a.max_steps, a.use_mask != 0, row);
+            const bool ended = player.step(e, row);
             const ScriptArgs& q = args_per_lane();
             if constexpr (TRAJ) {
                 const size_t r = (size_t)t0 * q.n + ep;
@@ -165,6 +179,12 @@ __global__ void __launch_bounds__(kScriptBlock) scripted_kernel(ScriptArgs a) {
             }
         }
     }
+}
+
+// The script's kind is kernel-uniform.  Under PRIORITY the policy stream is neither read nor written.
+template <class G, bool TRAJ>
+__global__ void __launch_bounds__(kScriptBlock) scripted_kernel(ScriptArgs a) {
+    play_episodes<G, TRAJ>(ScriptPlayer<G>{a});
 }
 
 int sfail(int code, const std::string& msg) { return g2048_internal::set_error(code, msg.c_str()); }
