@@ -4,7 +4,9 @@
 // (integer / indexing work, no MFMA; DESIGN.md "Kernels" has its roofline):
 //   * two row tables are staged once per workgroup into LDS and fill it exactly (160 KiB): the move-left image
 //     of every 4-nibble line (65,536 x uint16) and its 4-bit merge code (which output cells are merge results),
-//     so a move is 4 x (one u16 + one nibble LDS lookup) with the merge summary read off the new line;
+//     so a move is 4 x (one u16 + one nibble LDS lookup) with the merge summary read off the new line; with log2
+//     rewards (the bench's form) a 16 KiB table over three cells takes their place: 4 x one u32 lookup and a
+//     short append step for the fourth cell (g2048_core.h board_move_lean3);
 //   * action mask and done are 64-bit SWAR expressions sharing one set of neighbour masks;
 //   * the spawn draws the k-th empty cell by popcount bisection (numpy-PCG64 stream in parity mode,
 //     Philox4x32-10 in throughput mode);
@@ -13,8 +15,7 @@
 //   * observations are written wave-cooperatively (every store instruction is 1 KiB of contiguous obs; the
 //     owning board comes from its lane through a cross-lane shuffle);
 //   * 32-bit byte offsets on SGPR bases (the launcher splits calls above kMaxLanesPerLaunch lanes).
-// Workgroups are persistent (one 1024-thread workgroup per CU: the LDS tables allow one), so the table fill
-// is paid once per CU per launch.
+// Workgroups are persistent (one 1024-thread workgroup per CU), so the table fill is paid once per CU per launch.
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
@@ -35,7 +36,8 @@ namespace {
 thread_local std::string g_err;
 std::mutex g_mu;
 constexpr int kMaxDev = 64;
-uint8_t* g_tab[kMaxDev] = {};   // [65536 x u16 line table][32768 x u8 merge codes][32768 x u8 max-merge fields]
+// [65536 x u16 line table][32768 x u8 merge codes][32768 x u8 max-merge fields][4096 x u32 three-cell line table]
+uint8_t* g_tab[kMaxDev] = {};
 int g_cus[kMaxDev] = {};
 
 int fail(int code, const std::string& msg) {
@@ -58,7 +60,9 @@ int fail(int code, const std::string& msg) {
 #endif
 #if G2048_DIAG
 // per-workgroup phase timestamps of the last step launch (s_memrealtime, 100 MHz): entry, tables filled,
-// main loop done, reset list built, end
+// main loop done, reset list built, end.  Thread 0 writes them.  RK 0: "main loop done" follows the barrier after
+// the last sweep (the workgroup's slowest wave).  RK 1: it follows thread 0's own last sweep and append, and "reset
+// list built" the one barrier, so their difference is wave 0's wait for the slowest wave.
 constexpr int kDiagSlots = 5, kDiagBlocks = 4096;
 __device__ uint64_t g_diag_ts[kDiagBlocks * kDiagSlots];
 #define G2048_TS(slot)                                                                          \
@@ -72,15 +76,21 @@ __device__ uint64_t g_diag_ts[kDiagBlocks * kDiagSlots];
     } while (0)
 #endif
 
-constexpr int kBlock = 1024;                  // 16 waves per CU; one workgroup per CU (160 KiB of LDS tables)
+constexpr int kBlock = 1024;                  // 16 waves per CU; one workgroup per CU (registers: 4 waves per SIMD)
 constexpr int kLines = 65536;
-constexpr int kTabBytes = kLines * 2 + kLines / 2;   // 163,840 B = the whole LDS of a gfx950 CU
+constexpr int kTabBytes = kLines * 2 + kLines / 2;   // 163,840 B = the whole LDS of a gfx950 CU (RK 0's tables)
 constexpr int kTabVec = kTabBytes / 16;
 // the device table in global memory: the line table, the merge codes (board_move_coded: the general reward path,
-// the move / rollout kernels) and the max-merge fields (board_move_lean: the log2-reward step path).  A step
-// kernel stages the line table and ONE of the two 4-bit tables in LDS (160 KiB).
+// the move / rollout kernels) and the max-merge fields (board_move_lean).  The general step kernel (RK 0) stages the
+// line table and the merge codes in LDS (160 KiB).
 constexpr int kMxOff = kTabBytes;
-constexpr int kDevTabBytes = kTabBytes + kLines / 2;
+// ... and the three-cell line table (g2048_core.h line3_entry: 4,096 x u32 = 16 KiB), which the log2-reward step
+// path (RK 1) stages instead of the 160 KiB: one uint4 per thread of a 1024-thread workgroup
+constexpr int kTab3Off = kTabBytes + kLines / 2;
+constexpr int kTab3Bytes = (int)kLine3Entries * 4;
+constexpr int kTab3Vec = kTab3Bytes / 16;
+constexpr int kDevTabBytes = kTab3Off + kTab3Bytes;
+static_assert(kTab3Off % 16 == 0, "the three-cell table is copied as uint4");
 constexpr int kLutSmallN = 16384;             // below this many lanes the tables are read through L1/L2
 constexpr int64_t kMaxLanesPerLaunch = int64_t(1) << 27;   // keeps every byte offset (<= 16 B/lane) in 32 bits
 
@@ -108,6 +118,11 @@ struct LineFn {
 struct CodeFn {   // a 4-bit-per-line table: merge codes or max-merge fields
     const uint8_t* code;
     __device__ uint32_t operator()(uint32_t o) const { return (code[o >> 1] >> ((o & 1u) << 2)) & 15u; }
+};
+
+struct Line3Fn {   // the three-cell line table (line3_entry)
+    const uint32_t* tab3;
+    __device__ uint32_t operator()(uint32_t o3) const { return tab3[o3]; }
 };
 
 __device__ inline uint64_t shfl64(uint64_t v, int src) {
@@ -326,11 +341,13 @@ __device__ inline void load_lane(const StepArgs& a, uint32_t i, LaneIn& x) {
 // as spilled 64-bit lane masks), 1 = any of the first three, 2 = the merged list too; 3 = as 0 with the action
 // mask written packed (mask_bits) instead of as int8[4].
 // RK (reward kind, chosen by the launcher): 0 = any config, `code` is the merge-code table (board_move_coded);
-// 1 = reward_mode "log2" with XO 0 / 3, `code` is the max-merge field table (board_move_lean: no merge decode,
-// no score, count and sum_e from board aggregates, the moved board's nz bits reused by the spawn and the masks).
+// 1 = reward_mode "log2" with XO 0 / 3: the move reads the three-cell line table `tab3` alone (board_move_lean3:
+// one read per line, no merge decode, no score, count and sum_e from board aggregates, the moved board's nz bits
+// reused by the spawn and the masks); `lut` and `code` are not read.
 template <int RNG, int XO, int RK>
 __device__ inline uint64_t step_lane(const StepArgs& a, uint32_t i, LaneIn& x, const LineFn& lut,
-                                     const CodeFn& code, bool& wobs, bool& reset, uint32_t& mbits) {
+                                     const CodeFn& code, const Line3Fn& tab3, bool& wobs, bool& reset,
+                                     uint32_t& mbits) {
     static_assert(RK == 0 || XO == 0 || XO == 3, "the lean path writes no score / merged list");
     constexpr bool LIST = XO == 2, EXTRA = XO == 1 || XO == 2;
     const g2048_lanes& L = a.L;
@@ -359,7 +376,7 @@ __device__ inline uint64_t step_lane(const StepArgs& a, uint32_t i, LaneIn& x, c
         m = b ^ ((uint64_t)x.act << 60);
         nzm = nz_bits(m);
     } else if constexpr (RK == 1) {
-        m = board_move_lean(b, x.act, lut, code, s, nzm);
+        m = board_move_lean3(b, x.act, tab3, s, nzm);
     } else {
         m = board_move_coded<LIST>(b, x.act, lut, code, s);
     }
@@ -424,12 +441,13 @@ __device__ inline uint64_t step_lane(const StepArgs& a, uint32_t i, LaneIn& x, c
 // A lane's first pending reset has its seed read here (`pseed`), so the read is long complete at the tail.
 template <int OBS, int RNG, int XO, int RK>
 __device__ __forceinline__ void sweep(const StepArgs& a, uint32_t w0, int lane, LaneIn& x, const LineFn& lut,
-                                      const CodeFn& code, uint64_t& pending, uint64_t& pseed, uint32_t k) {
+                                      const CodeFn& code, const Line3Fn& tab3, uint64_t& pending, uint64_t& pseed,
+                                      uint32_t k) {
     const uint32_t i = w0 + lane;
     bool wobs = false, reset = false;
     uint32_t mbits = 0;
     uint64_t b = 0;
-    if (i < a.n) b = step_lane<RNG, XO, RK>(a, i, x, lut, code, wobs, reset, mbits);
+    if (i < a.n) b = step_lane<RNG, XO, RK>(a, i, x, lut, code, tab3, wobs, reset, mbits);
     if (reset) {
         if (!pending) {
             if constexpr (RNG == G2048_RNG_PCG64) pseed = ld(a.L.seed, i);
@@ -456,6 +474,45 @@ constexpr int kStepLdsVec = kStepLdsBytes / 16;
 constexpr int kResetCap = (kStepLdsBytes - 16) / 12;
 static_assert(16 + kResetCap * 4 + kResetCap * 8 <= kStepLdsBytes, "reset list fits the LDS area");
 static_assert(kTabVec % kBlock == 0, "table fill: whole chunks per thread");
+// RK 1 (the three-cell table): 16 KiB of table and, beside it, a reset list of the workgroup's own -- 4 entries per
+// thread, the workgroup's whole share of a 1M-board launch on 256 CUs (every lane truncating in one step stays a
+// dense pass; tests/test_gpu_step_line3.py overflows it into the per-lane fallback with 5 sweeps per wave)
+constexpr int kReset3Cap = 4 * kBlock;
+constexpr int kList3Off = kTab3Bytes;                                 // counter (16 B), indices, seeds
+constexpr int kStep3LdsVec = (kTab3Bytes + 16 + kReset3Cap * 12) / 16;
+static_assert(kTab3Vec == kBlock, "table fill: one uint4 per thread");
+
+// The deferred auto-resets of one wave, compacted into the workgroup's LDS list (counter, lane indices, previous
+// seeds; `cap` entries).  A lane whose entry does not fit does its own reset (mass reset).
+template <int OBS, int RNG>
+__device__ __forceinline__ void append_resets(const StepArgs& a, uint64_t pending, uint64_t pseed, uint32_t w_first,
+                                              uint32_t wstride, int lane, uint32_t* cnt, uint32_t* ridx,
+                                              uint64_t* rseed, uint32_t cap) {
+    bool first = true;
+    while (__ballot(pending != 0ull)) {    // wave-uniform; one round per pending board of the busiest lane
+        const bool has = pending != 0ull;
+        const uint32_t kk = has ? (uint32_t)__builtin_ctzll(pending) : 0u;
+        const uint32_t i = w_first + kk * wstride + lane;
+        const uint64_t sd = first ? pseed : (has ? ld(a.L.seed, i) : 0ull);
+        const uint64_t bal = __ballot(has);
+        const int leader = __builtin_ctzll(bal);
+        uint32_t base = 0;
+        if (lane == leader) base = atomicAdd(cnt, (uint32_t)__popcll(bal));
+        base = (uint32_t)__shfl((int)base, leader, 64);
+        const uint32_t slot =
+            base + __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
+        if (has) {
+            if (slot < cap) {
+                ridx[slot] = i;
+                rseed[slot] = sd;
+            } else {
+                reset_lane<OBS, RNG>(a, i, sd);   // list full (mass reset): the lane does its own
+            }
+            pending &= pending - 1ull;
+        }
+        first = false;
+    }
+}
 
 // Persistent over the board array, one board per lane per sweep (wave g of W takes the chunks of 64 boards
 // g, g + W, g + 2W, ...), software-pipelined with three register buffers A / B / C (no back-edge copy, which
@@ -463,13 +520,22 @@ static_assert(kTabVec % kBlock == 0, "table fill: whole chunks per thread");
 // Prefetch loads are issued unconditionally from a clamped lane index (lanes past n re-read lane n-1 and compute
 // nothing): a load skipped on some path would make the compiler's vmcnt accounting assume that path and wait for
 // every load in flight, including those of the sweeps being prefetched.
-// LDS: stage the two row tables in LDS, else read them through L1/L2 (small batches).  The first two sweeps'
-// loads are issued before the table fill; each workgroup fills its 10 chunks starting at a different one
-// (blockIdx % 10), so the CUs sharing an L2 do not read the same lines at once.  Sweeps per wave <= 64
-// (launcher): the `pending` reset bitmask.
+// LDS: stage the row tables in LDS, else read them through L1/L2 (small batches).  The first two sweeps' loads are
+// issued before the table fill.  Sweeps per wave <= 64 (launcher): the `pending` reset bitmask.
+// RK 0 (any reward): the line table and the merge codes, 160 KiB = the whole LDS; each workgroup fills its 10
+// chunks starting at a different one (blockIdx % 10), so the CUs sharing an L2 do not read the same lines at once.
 // Auto-resets are deferred to the end.  With the LDS tables dead after the last sweep, the block compacts its
 // pending resets into an LDS list and runs them densely (thread t takes entries t, t + 1024, ...): ~30 resets
 // of a 1M-board step per CU cost one pass of one wave instead of one divergent pass in most of the 16 waves.
+// RK 1 (log2 rewards): the move reads the three-cell line table alone, 16 KiB, staged with one uint4 per thread (or
+// read through L1 below kLutSmallN: it fits the 32 KiB L1).  The reset list has an LDS region of its own beside the
+// table: the counter is zeroed at entry (the fill's barrier publishes it), each wave appends its pending resets
+// right after its last sweep, and one barrier precedes the dense pass -- no wave waits for "every wave is past its
+// last table read".  Measured at 1M boards, 200 launches, interleaved (profiles/step_line3/): 29.7 us against the
+// 160 KiB tables' 30.9-31.3.  Tried on top and rejected there: four 256-thread workgroups per CU, each with its own
+// table, list and barriers (29.9-31.0 us against 28.8-30.2 in the same rounds: the short workgroups' loops run
+// 13.7 us at the median against 9.5); the table's load issued before the first sweeps' loads, so that the fill waits
+// for it alone (29.5-29.9 against 29.7-29.8: no difference).
 // (A dynamic schedule -- chunks claimed with device-scope atomics -- measured slower on MI355X: under this
 // kernel's streaming load an atomic's return takes microseconds, and same-address atomics serialize.)
 // (Round 4: an XCD-aware static partition -- contiguous chunk ranges, larger for the early-dispatched XCD groups --
@@ -477,7 +543,8 @@ static_assert(kTabVec % kBlock == 0, "table fill: whole chunks per thread");
 template <int OBS, int RNG, bool LDS, int XO, int U, int RK>
 __global__ void __launch_bounds__(kBlock) step_kernel(StepArgs a) {
     static_assert(U == 1, "one board per lane per sweep");
-    __shared__ uint4 tab_lds[LDS ? kStepLdsVec : 1];
+    constexpr bool LDS3 = LDS && RK == 1;
+    __shared__ uint4 tab_lds[LDS3 ? kStep3LdsVec : LDS ? kStepLdsVec : 1];
     const int lane = threadIdx.x & 63;
     const uint32_t w_first = (blockIdx.x * kBlock + threadIdx.x) & ~63u;
     const uint32_t wstride = gridDim.x * kBlock;
@@ -490,7 +557,14 @@ __global__ void __launch_bounds__(kBlock) step_kernel(StepArgs a) {
     load_lane<RNG>(a, lane_at(w0), A);
     load_lane<RNG>(a, lane_at(w1), B);
     const uint8_t* tab = a.tab;
-    if constexpr (LDS) {
+    const uint32_t* tab3 = reinterpret_cast<const uint32_t*>(a.tab + kTab3Off);
+    if constexpr (LDS3) {
+        const uint4* src = reinterpret_cast<const uint4*>(a.tab + kTab3Off);
+        if (threadIdx.x == 0) tab_lds[kList3Off / 16] = make_uint4(0u, 0u, 0u, 0u);   // the list's counter
+        if (!(G2048_DIAG && (a.diag & 1))) tab_lds[threadIdx.x] = src[threadIdx.x];
+        __syncthreads();
+        tab3 = reinterpret_cast<const uint32_t*>(tab_lds);
+    } else if constexpr (LDS) {
         const uint4* src = reinterpret_cast<const uint4*>(a.tab);
         if (!(G2048_DIAG && (a.diag & 1))) {
             constexpr uint32_t kChunks = kTabVec / kBlock;
@@ -500,8 +574,7 @@ __global__ void __launch_bounds__(kBlock) step_kernel(StepArgs a) {
                 uint32_t c = j + rot;
                 c -= c >= kChunks ? kChunks : 0u;
                 const uint32_t k = c * kBlock + threadIdx.x;
-                // chunks 8, 9 = the 4-bit table: merge codes (RK 0) or max-merge fields (RK 1, kMxOff)
-                tab_lds[k] = src[k + (RK == 1 && c >= 8u ? (uint32_t)((kMxOff - 2 * kLines) / 16) : 0u)];
+                tab_lds[k] = src[k];       // chunks 8, 9 = the merge codes
             }
         }
         __syncthreads();
@@ -509,27 +582,39 @@ __global__ void __launch_bounds__(kBlock) step_kernel(StepArgs a) {
     }
     G2048_TS(1);
     const LineFn lut{reinterpret_cast<const uint16_t*>(tab)};
-    const CodeFn code{tab + (LDS || RK == 0 ? 2 * kLines : kMxOff)};
+    const CodeFn code{tab + 2 * kLines};       // the merge codes (RK 0); RK 1 reads tab3 alone
+    const Line3Fn t3{tab3};
     uint64_t pending = 0, pseed = 0;
     uint32_t k = 0;
     while (w0 < wend) {                        // wave-uniform
         const uint32_t w2 = w1 + wstride;
         load_lane<RNG>(a, lane_at(w2), C);
-        sweep<OBS, RNG, XO, RK>(a, w0, lane, A, lut, code, pending, pseed, k);
+        sweep<OBS, RNG, XO, RK>(a, w0, lane, A, lut, code, t3, pending, pseed, k);
         if (w1 >= wend) break;
         const uint32_t w3 = w2 + wstride;
         load_lane<RNG>(a, lane_at(w3), A);
-        sweep<OBS, RNG, XO, RK>(a, w1, lane, B, lut, code, pending, pseed, k + 1);
+        sweep<OBS, RNG, XO, RK>(a, w1, lane, B, lut, code, t3, pending, pseed, k + 1);
         if (w2 >= wend) break;
         const uint32_t w4 = w3 + wstride;
         load_lane<RNG>(a, lane_at(w4), B);
-        sweep<OBS, RNG, XO, RK>(a, w2, lane, C, lut, code, pending, pseed, k + 2);
+        sweep<OBS, RNG, XO, RK>(a, w2, lane, C, lut, code, t3, pending, pseed, k + 2);
         w0 = w3;
         w1 = w4;
         k += 3;
     }
     if (G2048_DIAG && (a.diag & 2)) pending = 0;
-    if constexpr (LDS) {
+    if constexpr (LDS3) {
+        constexpr uint32_t kCap = (uint32_t)kReset3Cap;
+        uint32_t* cnt = reinterpret_cast<uint32_t*>(tab_lds + kList3Off / 16);
+        uint32_t* ridx = cnt + 4;
+        uint64_t* rseed = reinterpret_cast<uint64_t*>(ridx + kCap);
+        append_resets<OBS, RNG>(a, pending, pseed, w_first, wstride, lane, cnt, ridx, rseed, kCap);
+        G2048_TS(2);                           // this wave's loop and append are done
+        __syncthreads();                       // the list is complete
+        G2048_TS(3);
+        const uint32_t R = *cnt < kCap ? *cnt : kCap;
+        for (uint32_t r = threadIdx.x; r < R; r += kBlock) reset_lane<OBS, RNG>(a, ridx[r], rseed[r]);
+    } else if constexpr (LDS) {
         uint32_t* cnt = reinterpret_cast<uint32_t*>(tab_lds);
         uint32_t* ridx = cnt + 4;
         uint64_t* rseed = reinterpret_cast<uint64_t*>(ridx + kResetCap + (kResetCap & 1));
@@ -537,30 +622,7 @@ __global__ void __launch_bounds__(kBlock) step_kernel(StepArgs a) {
         G2048_TS(2);
         if (threadIdx.x == 0) *cnt = 0u;
         __syncthreads();
-        bool first = true;
-        while (__ballot(pending != 0ull)) {    // wave-uniform; one round per pending board of the busiest lane
-            const bool has = pending != 0ull;
-            const uint32_t kk = has ? (uint32_t)__builtin_ctzll(pending) : 0u;
-            const uint32_t i = w_first + kk * wstride + lane;
-            const uint64_t sd = first ? pseed : (has ? ld(a.L.seed, i) : 0ull);
-            const uint64_t bal = __ballot(has);
-            const int leader = __builtin_ctzll(bal);
-            uint32_t base = 0;
-            if (lane == leader) base = atomicAdd(cnt, (uint32_t)__popcll(bal));
-            base = (uint32_t)__shfl((int)base, leader, 64);
-            const uint32_t slot =
-                base + __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
-            if (has) {
-                if (slot < (uint32_t)kResetCap) {
-                    ridx[slot] = i;
-                    rseed[slot] = sd;
-                } else {
-                    reset_lane<OBS, RNG>(a, i, sd);   // list full (mass reset): the lane does its own
-                }
-                pending &= pending - 1ull;
-            }
-            first = false;
-        }
+        append_resets<OBS, RNG>(a, pending, pseed, w_first, wstride, lane, cnt, ridx, rseed, (uint32_t)kResetCap);
         __syncthreads();
         G2048_TS(3);
         const uint32_t R = *cnt < (uint32_t)kResetCap ? *cnt : (uint32_t)kResetCap;
@@ -920,7 +982,7 @@ int g2048_init(int device) {
     int prev = 0;
     G2048_HIP(hipGetDevice(&prev));
     G2048_HIP(hipSetDevice(device));
-    static uint8_t host[kDevTabBytes];
+    alignas(16) static uint8_t host[kDevTabBytes];
     uint16_t* line = reinterpret_cast<uint16_t*>(host);
     uint8_t* code = host + 2 * kLines;
     uint8_t* mx = host + kMxOff;
@@ -935,6 +997,8 @@ int g2048_init(int device) {
             mx[r >> 1] = (uint8_t)f;
         }
     }
+    uint32_t* tab3 = reinterpret_cast<uint32_t*>(host + kTab3Off);
+    for (uint32_t o3 = 0; o3 < kLine3Entries; o3++) tab3[o3] = line3_entry(o3);
     uint8_t* d = nullptr;
     hipError_t e = hipMalloc(&d, sizeof(host));
     if (e == hipSuccess) e = hipMemcpy(d, host, sizeof(host), hipMemcpyHostToDevice);

@@ -442,6 +442,90 @@ G2048_HD uint64_t board_move_lean(uint64_t b, uint32_t a, const Lut& lut, const 
     return g;
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// Three-cell line table (the step kernel's log2-reward path): 4,096 x u32 = 16 KiB instead of the 160 KiB of the
+// line table and the max-merge fields.  Moving left takes the tiles in order, so cell 3 (`d`) meets only the
+// last tile that cells 0..2 leave behind, and merges with it only if that tile is not itself a merge product.
+// Entry of o3 = cells 0..2:
+//   [0,16)  r  = line_move_left(o3) (three cells: bits 12..15 are 0)
+//   [16,21) m  = the last tile of r if it is not a merge product, else 16 (equal to no nibble; an empty r too)
+//   [21,25) f  = line_max_merge_field(o3)
+//   [25,29) sh = 4 * tiles(r): where an unmerged d lands
+// line3_append gives the whole line's move and field from the entry and d.
+// ---------------------------------------------------------------------------------------------------------
+constexpr uint32_t kLine3Entries = 4096u;
+
+G2048_HD uint32_t line3_entry(uint32_t o3) {
+    uint32_t r = 0u, k = 0u, last = 16u, pend = 0u;   // pend: a placed tile that may still merge
+    for (int c = 0; c < 3; c++) {
+        const uint32_t v = (o3 >> (4 * c)) & 15u;
+        if (!v) continue;
+        if (pend == v) {                               // merges into the last placed tile (saturating at 15)
+            r += (v < 15u ? 1u : 0u) << (4u * (k - 1u));
+            pend = 0u;
+            last = 16u;
+        } else {
+            r |= v << (4u * k);
+            k++;
+            pend = v;
+            last = v;
+        }
+    }
+    return r | (last << 16) | (line_max_merge_field(o3 & 0xFFFu) << 21) | ((4u * k) << 25);
+}
+
+// the moved line (16 bits) and the max-merge field of the line o3 | d << 12, from o3's entry
+G2048_HD uint32_t line3_append(uint32_t e, uint32_t d, uint32_t& field) {
+    const uint32_t m = bfe32(e, 16u, 5u), f = bfe32(e, 21u, 4u), sh = bfe32(e, 25u, 4u);
+    const bool mg = d == m;                            // d != 0 here: m is never 0
+    const uint32_t inc = (d < 15u ? 1u : 0u);          // 15 + 15 stays 15
+    const uint32_t nw = mg ? e + ((inc << sh) >> 4) : (e | (d << sh));
+    const uint32_t dm = mg ? d : 0u;                   // merged exponent d + 1: field d (15 = saturated)
+    field = f > dm ? f : dm;
+    return nw & 0xFFFFu;
+}
+
+// board_move_lean with the three-cell table (`tab3(o3)` -> line3_entry(o3)): the same board, count, sum_e, max_e,
+// overflow and nzg, from one table read per line.
+template <class Tab3>
+G2048_HD uint64_t board_move_lean3(uint64_t b, uint32_t a, const Tab3& tab3, MoveSummary& s, uint64_t& nzg) {
+    const uint64_t mvert = 0ull - (uint64_t)((a == 0u) | (a == 2u));
+    const uint64_t mrev = 0ull - (uint64_t)((a == 1u) | (a == 2u));
+    uint64_t f = b ^ ((b ^ transpose(b)) & mvert);
+    f ^= (f ^ reverse_rows(f)) & mrev;
+    uint32_t o[4], e[4], nw[4], fm[4];
+#pragma unroll
+    for (int j = 0; j < 4; j++) o[j] = (uint32_t)(f >> (16 * j)) & 0xFFFFu;
+#pragma unroll
+    for (int j = 0; j < 4; j++) e[j] = (uint32_t)tab3(o[j] & 0xFFFu);
+#pragma unroll
+    for (int j = 0; j < 4; j++) nw[j] = line3_append(e[j], o[j] >> 12, fm[j]);
+    uint64_t g = 0;
+#pragma unroll
+    for (int j = 0; j < 4; j++) g |= (uint64_t)nw[j] << (16 * j);
+    const uint32_t m01 = fm[0] > fm[1] ? fm[0] : fm[1], m23 = fm[2] > fm[3] ? fm[2] : fm[3];
+    const uint32_t mf = m01 > m23 ? m01 : m23;
+    g ^= (g ^ reverse_rows(g)) & mrev;
+    g ^= (g ^ transpose(g)) & mvert;
+    nzg = nz_bits(g);
+    s.max_e = mf ? mf + 1u : 0u;
+    s.overflow = mf == 15u;
+    s.count = (uint32_t)(popc64(nz_bits(b)) - popc64(nzg));
+    s.sum_e = nib_sum64(b) - nib_sum64(g) + 2u * s.count;
+    if (s.overflow) {  // a saturated 15+15 merge: the aggregate is off by one per such merge; sum the lines
+        uint32_t se = 0;
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            const LineMerges m = line_merges(o[j], nw[j]);
+            se += m.e0 + m.e1;
+        }
+        s.sum_e = se;
+    }
+    s.score = 0u;
+    s.list = 0u;
+    return g;
+}
+
 // nz / equal-neighbour masks of a board, shared by is_done and action_mask
 struct BoardBits {
     uint64_t nz, z, eqh, eqv;
