@@ -447,4 +447,8 @@ int g2048_onehot_dw1(const uint64_t* boards, const float* d1, int h1, int64_t m,
  * interface */
 #include "g2048_search.h"
 
+/* the same player with one episode or board per wave instead of per lane: additive entry points of ABI 17, part of
+ * this interface */
+#include "g2048_search_wave.h"
+
 #endif /* G2048_H */

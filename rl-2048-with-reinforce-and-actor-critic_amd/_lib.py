@@ -32,7 +32,10 @@ SOURCES = [SRC, os.path.join(PKG_DIR, "csrc", "g2048_policy.hip"), os.path.join(
            os.path.join(PKG_DIR, "csrc", "g2048_sized_scripted.hip"),
            # whole episodes and single choices of the expectimax search player: 4 x 4 and sizes 2..8
            os.path.join(PKG_DIR, "csrc", "g2048_search.hip"),
-           os.path.join(PKG_DIR, "csrc", "g2048_sized_search.hip")]
+           os.path.join(PKG_DIR, "csrc", "g2048_sized_search.hip"),
+           # the same player with one episode / one board per wave (depth 1 and 2): 4 x 4 and sizes 2..8
+           os.path.join(PKG_DIR, "csrc", "g2048_search_wave.hip"),
+           os.path.join(PKG_DIR, "csrc", "g2048_sized_search_wave.hip")]
 INCLUDE = os.path.join(REPO_ROOT, "include")
 ABI_VERSION = 17
 DEEP_MAX_HIDDEN = 4
@@ -86,7 +89,7 @@ def _object_for(src: str, flags: list[str]) -> str:
     hdrs = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".inc")))
     for f in [src] + hdrs + [os.path.join(INCLUDE, "g2048.h"), os.path.join(INCLUDE, "g2048_sized.h"),
                                 os.path.join(INCLUDE, "g2048_eval.h"), os.path.join(INCLUDE, "g2048_scripted.h"),
-                                os.path.join(INCLUDE, "g2048_search.h")]:
+                                os.path.join(INCLUDE, "g2048_search.h"), os.path.join(INCLUDE, "g2048_search_wave.h")]:
         with open(f, "rb") as fh:
             h.update(fh.read())
     return os.path.join(BUILD_DIR, f"{os.path.splitext(os.path.basename(src))[0]}-{h.hexdigest()[:16]}.o")
@@ -286,7 +289,9 @@ def _declare(L):
     L.g2048_sized_search_eval.argtypes = [i32, P(Search)] + L.g2048_sized_scripted_eval.argtypes[2:]
     L.g2048_search_choose.argtypes = [P(Search), vp, i64, vp, vp, vp]
     L.g2048_sized_search_choose.argtypes = [i32, P(Search), vp, i64, vp, vp, vp]
-    for name in SIZED_SYMBOLS + EVAL_SYMBOLS + SCRIPTED_SYMBOLS + SEARCH_SYMBOLS:
+    for name, sibling in zip(SEARCH_WAVE_SYMBOLS, SEARCH_SYMBOLS):
+        getattr(L, name).argtypes = getattr(L, sibling).argtypes
+    for name in SIZED_SYMBOLS + EVAL_SYMBOLS + SCRIPTED_SYMBOLS + SEARCH_SYMBOLS + SEARCH_WAVE_SYMBOLS:
         getattr(L, name).restype = ctypes.c_int
     for name in ("g2048_init", "g2048_seed_pcg64", "g2048_reset", "g2048_step", "g2048_obs", "g2048_move",
                  "g2048_sample", "g2048_returns", "g2048_symmetries", "g2048_policy_pack", "g2048_policy",
@@ -325,6 +330,11 @@ SCRIPTED_SYMBOLS = ("g2048_scripted_rollout", "g2048_scripted_eval", "g2048_size
 # include/g2048_search.h (included by g2048.h): whole episodes and single choices of the expectimax search player
 SEARCH_SYMBOLS = ("g2048_search_rollout", "g2048_search_eval", "g2048_sized_search_rollout", "g2048_sized_search_eval",
                   "g2048_search_choose", "g2048_sized_search_choose")
+
+# include/g2048_search_wave.h (included by g2048.h): the search player with one episode / one board per wave; entry i
+# has the signature of SEARCH_SYMBOLS[i]
+SEARCH_WAVE_SYMBOLS = ("g2048_search_wave_rollout", "g2048_search_wave_eval", "g2048_sized_search_wave_rollout",
+                       "g2048_sized_search_wave_eval", "g2048_search_wave_choose", "g2048_sized_search_wave_choose")
 
 
 def lib():

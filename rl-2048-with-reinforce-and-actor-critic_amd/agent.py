@@ -1506,6 +1506,21 @@ class ReinforceAgent:
                                 "lane, no trajectory rows, suspended episodes resumed)",
                                 "search_rollout", "search_max_workgroups", sized=True, search=True,
                                 budget="search_step_budget"),
+        # search_cooperative: the same buffers and suspend / resume protocol, so the same driver and tuning
+        "search_wave": _Family("g2048_search_wave_rollout", "g2048_search_wave_eval",
+                               "g2048_search_wave_rollout (persistent launches, one episode per wave, its expectimax "
+                               "spread over the lanes, suspended episodes resumed)",
+                               "g2048_search_wave_eval (persistent launches, one episode per wave, its expectimax "
+                               "spread over the lanes, no trajectory rows, suspended episodes resumed)",
+                               "search_rollout", "search_max_workgroups", search=True, budget="search_step_budget"),
+        "sized_search_wave": _Family("g2048_sized_search_wave_rollout", "g2048_sized_search_wave_eval",
+                                     "g2048_sized_search_wave_rollout (persistent launches, one episode per wave, its "
+                                     "expectimax spread over the lanes, suspended episodes resumed)",
+                                     "g2048_sized_search_wave_eval (persistent launches, one episode per wave, its "
+                                     "expectimax spread over the lanes, no trajectory rows, suspended episodes "
+                                     "resumed)",
+                                     "search_rollout", "search_max_workgroups", sized=True, search=True,
+                                     budget="search_step_budget"),
     }
 
     # g2048_deep_rollout (any depth, 4 x 4): its first trajectory capacity when max_steps is None (doubled while
@@ -1541,6 +1556,13 @@ class ReinforceAgent:
     search_rollout_cap0 = 256
     search_rollout_max_rows = 1 << 24
     search_step_budget = 256
+    # Search play, wave-cooperative: one episode (search_actions: one board) per wave of 64 lanes instead of per lane
+    # (g2048_*search_wave_*), for an ExpectimaxPolicy of depth >= 1; depth 0 keeps the per-lane kernels.  The results
+    # are bit for bit the per-lane path's.  Off by default, like the use_fused_* switches: it is the faster path for a
+    # launch that leaves the device mostly idle one episode per lane (a single run_episode, an evaluation of tens to
+    # thousands of episodes) and the slower one once the per-lane form fills the device: measured at 4 x 4 depth 1, 18x
+    # faster at 64 episodes, 1.55x at 65,536, 0.58x at 524,288.  Shares the four attributes above.
+    search_cooperative = False
 
     def _persistent_family(self, rng: str, spec):
         """("fused" | "deep" | "sized", spec) of the persistent kernel family that plays the net's episodes under
@@ -1577,7 +1599,8 @@ class ReinforceAgent:
             raise ValueError("a PriorityPolicy needs env_config.use_action_mask=True on the batched path (its choice is "
                              "read off the action mask)")
         if isinstance(action_gen, ExpectimaxPolicy):     # computes validity itself: mask on or off
-            return "sized_search" if self._sized else "search"
+            wave = "_wave" if self.search_cooperative and action_gen.depth >= 1 else ""
+            return ("sized_search" if self._sized else "search") + wave
         return "sized_scripted" if self._sized else "scripted"
 
     def _play_persistent(self, family: str, spec, env_seeds, policy_seeds, use_greedy: bool, rows: bool,
@@ -1698,10 +1721,10 @@ class ReinforceAgent:
         q = torch.empty(m, 4, dtype=torch.int64, device=self.device)
         sp = policy._search()
         head = (self.size, ctypes.byref(sp)) if self._sized else (ctypes.byref(sp),)
-        fn = self._lib.g2048_sized_search_choose if self._sized else self._lib.g2048_search_choose
-        L.check(fn(*head, L.ptr(flat), m, L.ptr(actions), L.ptr(q), self._stream))
-        self._paths["search_actions"] = ("g2048_sized_search_choose" if self._sized else "g2048_search_choose") + \
-                                        " (one board per thread)"
+        wave = self.search_cooperative and policy.depth >= 1
+        name = ("g2048_sized_search" if self._sized else "g2048_search") + ("_wave_choose" if wave else "_choose")
+        L.check(getattr(self._lib, name)(*head, L.ptr(flat), m, L.ptr(actions), L.ptr(q), self._stream))
+        self._paths["search_actions"] = name + (" (one board per wave)" if wave else " (one board per thread)")
         return actions.view(shape), q.view(shape + (4,))
 
     def trajectories_from_batch(self, batch: TrajectoryBatch, with_states: bool = True) -> list[dict[str, Any]]:

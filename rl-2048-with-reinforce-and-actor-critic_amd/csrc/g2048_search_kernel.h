@@ -14,7 +14,7 @@
 // cells in an afterstate a depth-0 step is 4 moves, a depth-1 step 4 + 4 * (2 E * 4) moves, a depth-2 step
 // 4 + 4 * (2 E * (4 + 4 * (2 E * 4))) -- each level multiplies the work by about 8 E -- against two stores and no loads
 // per step: far from HBM, bound by VALU issue, and by instruction latency while the launch has few waves per SIMD.
-// A wave-cooperative form (one episode's children spread over the lanes) is not built.
+// The wave-cooperative form (one episode's children spread over the lanes of a wave) is g2048_search_wave_kernel.h.
 #pragma once
 #include "g2048_scripted_kernel.h"
 #include "g2048_search_core.h"
