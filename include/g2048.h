@@ -451,4 +451,8 @@ int g2048_onehot_dw1(const uint64_t* boards, const float* d1, int h1, int64_t m,
  * this interface */
 #include "g2048_search_wave.h"
 
+/* an n-tuple value network: its players (greedy and one chance layer) and the batched TD(0) update: additive entry
+ * points of ABI 17, part of this interface */
+#include "g2048_ntuple.h"
+
 #endif /* G2048_H */

@@ -12,8 +12,9 @@ The GPU work happens in libg2048.so (csrc/g2048.hip, C ABI in include/g2048.h); 
 from ._lib import build as build_library  # noqa: F401
 from .config import Game2048EnvConfig  # noqa: F401
 from .env import Game2048, Game2048Env  # noqa: F401
+from .ntuple import NTupleNetwork, NTuplePolicy  # noqa: F401
 from .policies import ExpectimaxPolicy, PriorityPolicy, UniformPolicy  # noqa: F401
 from .vec_env import VecGame2048Env, decode_merged  # noqa: F401
 
 __all__ = ["Game2048EnvConfig", "Game2048", "Game2048Env", "VecGame2048Env", "decode_merged", "build_library",
-           "PriorityPolicy", "UniformPolicy", "ExpectimaxPolicy"]
+           "PriorityPolicy", "UniformPolicy", "ExpectimaxPolicy", "NTupleNetwork", "NTuplePolicy"]

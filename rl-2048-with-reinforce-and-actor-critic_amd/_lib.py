@@ -35,7 +35,10 @@ SOURCES = [SRC, os.path.join(PKG_DIR, "csrc", "g2048_policy.hip"), os.path.join(
            os.path.join(PKG_DIR, "csrc", "g2048_sized_search.hip"),
            # the same player with one episode / one board per wave (depth 1 and 2): 4 x 4 and sizes 2..8
            os.path.join(PKG_DIR, "csrc", "g2048_search_wave.hip"),
-           os.path.join(PKG_DIR, "csrc", "g2048_sized_search_wave.hip")]
+           os.path.join(PKG_DIR, "csrc", "g2048_sized_search_wave.hip"),
+           # the n-tuple value network: its players, values and the batched TD(0) update: 4 x 4 and sizes 2..8
+           os.path.join(PKG_DIR, "csrc", "g2048_ntuple.hip"),
+           os.path.join(PKG_DIR, "csrc", "g2048_sized_ntuple.hip")]
 INCLUDE = os.path.join(REPO_ROOT, "include")
 ABI_VERSION = 17
 DEEP_MAX_HIDDEN = 4
@@ -55,6 +58,9 @@ SCRIPT_PRIORITY, SCRIPT_UNIFORM = 0, 1
 SCRIPT_BLOCK = 256
 # include/g2048_search.h
 SEARCH_MAX_DEPTH, SEARCH_MAX_WEIGHT = 2, 4096
+# include/g2048_ntuple.h
+NTUPLE_FRAC_BITS, NTUPLE_MAX_DEPTH, NTUPLE_MIN_CELLS, NTUPLE_MAX_CELLS, NTUPLE_MAX_FEATURES = 10, 1, 2, 6, 128
+NTUPLE_MAX_LR_NUM, NTUPLE_MAX_LR_SHIFT = 65536, 40
 
 
 CSRC = os.path.join(PKG_DIR, "csrc")
@@ -89,7 +95,8 @@ def _object_for(src: str, flags: list[str]) -> str:
     hdrs = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".inc")))
     for f in [src] + hdrs + [os.path.join(INCLUDE, "g2048.h"), os.path.join(INCLUDE, "g2048_sized.h"),
                                 os.path.join(INCLUDE, "g2048_eval.h"), os.path.join(INCLUDE, "g2048_scripted.h"),
-                                os.path.join(INCLUDE, "g2048_search.h"), os.path.join(INCLUDE, "g2048_search_wave.h")]:
+                                os.path.join(INCLUDE, "g2048_search.h"), os.path.join(INCLUDE, "g2048_search_wave.h"),
+                                os.path.join(INCLUDE, "g2048_ntuple.h")]:
         with open(f, "rb") as fh:
             h.update(fh.read())
     return os.path.join(BUILD_DIR, f"{os.path.splitext(os.path.basename(src))[0]}-{h.hexdigest()[:16]}.o")
@@ -187,6 +194,18 @@ class Search(ctypes.Structure):
     """g2048_search: the expectimax player of a launch (depth 0..2, four weights 0..4096)."""
     _fields_ = [("depth", ctypes.c_int32), ("w_merge", ctypes.c_uint32), ("w_empty", ctypes.c_uint32),
                 ("w_smooth", ctypes.c_uint32), ("w_corner", ctypes.c_uint32)]
+
+
+class NTupleFeature(ctypes.Structure):
+    """g2048_ntuple_feature: one feature of an n-tuple network (table offset, k cells)."""
+    _fields_ = [("offset", ctypes.c_uint32), ("k", ctypes.c_uint8), ("cells", ctypes.c_uint8 * 6),
+                ("reserved", ctypes.c_uint8)]
+
+
+class NTuple(ctypes.Structure):
+    """g2048_ntuple: the network of a call (depth 0..1, host feature list, device int32 weights)."""
+    _fields_ = [("depth", ctypes.c_int32), ("n_features", ctypes.c_int32), ("features", ctypes.POINTER(NTupleFeature)),
+                ("weights", ctypes.c_void_p), ("n_weights", ctypes.c_int64)]
 
 
 _lib = None
@@ -291,7 +310,19 @@ def _declare(L):
     L.g2048_sized_search_choose.argtypes = [i32, P(Search), vp, i64, vp, vp, vp]
     for name, sibling in zip(SEARCH_WAVE_SYMBOLS, SEARCH_SYMBOLS):
         getattr(L, name).argtypes = getattr(L, sibling).argtypes
-    for name in SIZED_SYMBOLS + EVAL_SYMBOLS + SCRIPTED_SYMBOLS + SEARCH_SYMBOLS + SEARCH_WAVE_SYMBOLS:
+    L.g2048_ntuple_rollout.argtypes = [P(NTuple)] + L.g2048_scripted_rollout.argtypes[1:]
+    L.g2048_ntuple_eval.argtypes = [P(NTuple)] + L.g2048_scripted_eval.argtypes[1:]
+    L.g2048_sized_ntuple_rollout.argtypes = [i32, P(NTuple)] + L.g2048_sized_scripted_rollout.argtypes[2:]
+    L.g2048_sized_ntuple_eval.argtypes = [i32, P(NTuple)] + L.g2048_sized_scripted_eval.argtypes[2:]
+    L.g2048_ntuple_choose.argtypes = [P(NTuple), vp, i64, vp, vp, vp]
+    L.g2048_sized_ntuple_choose.argtypes = [i32, P(NTuple), vp, i64, vp, vp, vp]
+    L.g2048_ntuple_values.argtypes = [P(NTuple), vp, i64, vp, vp]
+    L.g2048_sized_ntuple_values.argtypes = [i32, P(NTuple), vp, i64, vp, vp]
+    L.g2048_ntuple_td_update.argtypes = [P(NTuple), vp, vp, vp, vp, i64, i64, ctypes.c_int32, ctypes.c_int32, vp, vp, vp]
+    L.g2048_sized_ntuple_td_update.argtypes = [i32, P(NTuple), vp, i64, vp, vp, vp, i64, i64, ctypes.c_int32,
+                                               ctypes.c_int32, vp, vp, vp]
+    for name in (SIZED_SYMBOLS + EVAL_SYMBOLS + SCRIPTED_SYMBOLS + SEARCH_SYMBOLS + SEARCH_WAVE_SYMBOLS +
+                 NTUPLE_SYMBOLS):
         getattr(L, name).restype = ctypes.c_int
     for name in ("g2048_init", "g2048_seed_pcg64", "g2048_reset", "g2048_step", "g2048_obs", "g2048_move",
                  "g2048_sample", "g2048_returns", "g2048_symmetries", "g2048_policy_pack", "g2048_policy",
@@ -335,6 +366,11 @@ SEARCH_SYMBOLS = ("g2048_search_rollout", "g2048_search_eval", "g2048_sized_sear
 # has the signature of SEARCH_SYMBOLS[i]
 SEARCH_WAVE_SYMBOLS = ("g2048_search_wave_rollout", "g2048_search_wave_eval", "g2048_sized_search_wave_rollout",
                        "g2048_sized_search_wave_eval", "g2048_search_wave_choose", "g2048_sized_search_wave_choose")
+
+# include/g2048_ntuple.h (included by g2048.h): the n-tuple value network's players, values and TD(0) update
+NTUPLE_SYMBOLS = ("g2048_ntuple_rollout", "g2048_ntuple_eval", "g2048_sized_ntuple_rollout", "g2048_sized_ntuple_eval",
+                  "g2048_ntuple_choose", "g2048_sized_ntuple_choose", "g2048_ntuple_values", "g2048_sized_ntuple_values",
+                  "g2048_ntuple_td_update", "g2048_sized_ntuple_td_update")
 
 
 def lib():

@@ -59,6 +59,7 @@ class _Family(NamedTuple):
     scripted: bool = False  # played by a PriorityPolicy / UniformPolicy instead of a net
     search: bool = False    # played by an ExpectimaxPolicy instead of a net
     budget: str = "eval_step_budget"   # the agent attribute holding evaluate_batch's steps per launch
+    ntuple: bool = False    # played by an NTuplePolicy instead of a net
 
 
 @dataclass
@@ -1351,8 +1352,9 @@ class ReinforceAgent:
         """Play one episode per lane (env.reset(seed=env_seeds[i]), policy stream default_rng(policy_seeds[i]))
         until every lane terminates or truncates -- the batched equivalent of calling run_episode for each
         (env_seed, policy_seed) pair (runner.py:587-591).  Everything stays on the device.
-        action_gen: a PriorityPolicy / UniformPolicy / ExpectimaxPolicy plays the episodes instead of the net
-        (run_episode's action_gen, batched: g2048_scripted_rollout / g2048_search_rollout); use_greedy is then ignored,
+        action_gen: a PriorityPolicy / UniformPolicy / ExpectimaxPolicy / NTuplePolicy plays the episodes instead of the
+        net (run_episode's action_gen, batched: g2048_scripted_rollout / g2048_search_rollout / g2048_ntuple_rollout);
+        use_greedy is then ignored,
         as the reference ignores it when action_fn answers."""
         n = len(env_seeds)
         if len(policy_seeds) != n:
@@ -1521,6 +1523,19 @@ class ReinforceAgent:
                                      "resumed)",
                                      "search_rollout", "search_max_workgroups", sized=True, search=True,
                                      budget="search_step_budget"),
+        "ntuple": _Family("g2048_ntuple_rollout", "g2048_ntuple_eval",
+                          "g2048_ntuple_rollout (persistent launches, one episode per lane played by an n-tuple "
+                          "network, suspended episodes resumed)",
+                          "g2048_ntuple_eval (persistent launches, one episode per lane played by an n-tuple network, "
+                          "no trajectory rows, suspended episodes resumed)",
+                          "ntuple_rollout", "ntuple_max_workgroups", budget="ntuple_step_budget", ntuple=True),
+        "sized_ntuple": _Family("g2048_sized_ntuple_rollout", "g2048_sized_ntuple_eval",
+                                "g2048_sized_ntuple_rollout (persistent launches, one episode per lane played by an "
+                                "n-tuple network, suspended episodes resumed)",
+                                "g2048_sized_ntuple_eval (persistent launches, one episode per lane played by an "
+                                "n-tuple network, no trajectory rows, suspended episodes resumed)",
+                                "ntuple_rollout", "ntuple_max_workgroups", sized=True, budget="ntuple_step_budget",
+                                ntuple=True),
     }
 
     # g2048_deep_rollout (any depth, 4 x 4): its first trajectory capacity when max_steps is None (doubled while
@@ -1563,6 +1578,14 @@ class ReinforceAgent:
     # thousands of episodes) and the slower one once the per-lane form fills the device: measured at 4 x 4 depth 1, 18x
     # faster at 64 episodes, 1.55x at 65,536, 0.58x at 524,288.  Shares the four attributes above.
     search_cooperative = False
+    # N-tuple play (action_gen = NTuplePolicy): the grid cap, first trajectory capacity, most rows and evaluate_batch's
+    # steps per launch, of their own.  A depth-0 step is four moves and 4 x 8B gathers, so a launch may run long
+    # episodes to their end; a depth-1 step costs up to 8 x #empty times that, and the budget bounds such a launch.
+    # Estimates, not measurements.
+    ntuple_max_workgroups = 0
+    ntuple_rollout_cap0 = 512
+    ntuple_rollout_max_rows = 1 << 24
+    ntuple_step_budget = 2048
 
     def _persistent_family(self, rng: str, spec):
         """("fused" | "deep" | "sized", spec) of the persistent kernel family that plays the net's episodes under
@@ -1584,13 +1607,14 @@ class ReinforceAgent:
 
     def _check_scripted(self, action_gen, rng: str, record_probs: bool) -> str:
         """The refusals of the batched scripted path, before any device call; returns its family."""
+        from .ntuple import NTuplePolicy
         from .policies import ExpectimaxPolicy, PriorityPolicy, UniformPolicy
 
-        if not isinstance(action_gen, (PriorityPolicy, UniformPolicy, ExpectimaxPolicy)):
+        if not isinstance(action_gen, (PriorityPolicy, UniformPolicy, ExpectimaxPolicy, NTuplePolicy)):
             raise TypeError(
                 f"action_gen must be a PriorityPolicy, a UniformPolicy or an ExpectimaxPolicy on the batched path (got "
                 f"{type(action_gen).__name__}); run_episode(env_seed, policy_seed, action_gen=...) is the host path "
-                f"for arbitrary callables")
+                f"for arbitrary callables (an NTuplePolicy is accepted here too)")
         if rng != "pcg64":
             raise ValueError(f'scripted play (action_gen) runs on the PCG64 streams only (rng="pcg64"), got rng={rng!r}')
         if record_probs:
@@ -1601,7 +1625,20 @@ class ReinforceAgent:
         if isinstance(action_gen, ExpectimaxPolicy):     # computes validity itself: mask on or off
             wave = "_wave" if self.search_cooperative and action_gen.depth >= 1 else ""
             return ("sized_search" if self._sized else "search") + wave
+        if isinstance(action_gen, NTuplePolicy):         # computes validity itself: mask on or off
+            self._check_network(action_gen.network)
+            return "sized_ntuple" if self._sized else "ntuple"
         return "sized_scripted" if self._sized else "scripted"
+
+    def _check_network(self, network) -> None:
+        """An NTupleNetwork this agent can play or train: of the env's board size (the device is checked at the call)."""
+        from .ntuple import NTupleNetwork
+
+        if not isinstance(network, NTupleNetwork):
+            raise TypeError(f"network must be an NTupleNetwork (got {type(network).__name__})")
+        if network.size != self.env_config.size:
+            raise ValueError(f"the NTupleNetwork is of board size {network.size}, the env of size "
+                             f"{self.env_config.size}")
 
     def _play_persistent(self, family: str, spec, env_seeds, policy_seeds, use_greedy: bool, rows: bool,
                          record_probs: bool = False):
@@ -1615,6 +1652,8 @@ class ReinforceAgent:
         fn = getattr(lib, fam.rollout if rows else fam.evaluate)
         W = int(lib.g2048_sized_words(self.size)) if fam.sized else None
         # the buffers, in the order the code before this driver made them; seeds: held, unused, until this call returns
+        if fam.ntuple:       # a refusal: before any device work
+            self._check_network_device(spec.network)
         streams, seeds = rollouts.episode_streams(lib, env_seeds, policy_seeds, dev, self._stream)
         ms, max_rows, traj = self.env_config.max_steps, None, None
         if rows:
@@ -1631,8 +1670,8 @@ class ReinforceAgent:
         queue = torch.zeros(1, dtype=torch.int32, device=dev)
         cfg = env_cfg_struct(self.env_config)
         # the arguments before and after the part that changes from launch to launch
-        if fam.scripted or fam.search:
-            script = spec._search() if fam.search else spec._script()
+        if fam.scripted or fam.search or fam.ntuple:
+            script = spec._ntuple() if fam.ntuple else spec._search() if fam.search else spec._script()
             head = (ctypes.byref(script), ctypes.byref(cfg))
         elif family == "fused":
             head = (L.ptr(self._packed_policy(spec)), *spec, ctypes.byref(cfg), int(use_greedy))
@@ -1727,6 +1766,85 @@ class ReinforceAgent:
         self._paths["search_actions"] = name + (" (one board per wave)" if wave else " (one board per thread)")
         return actions.view(shape), q.view(shape + (4,))
 
+    def _check_network_device(self, network) -> None:
+        nd, dev = network.device, self.device
+        if nd.type != dev.type or (nd.index is not None and dev.index is not None and nd.index != dev.index):
+            raise ValueError(f"the NTupleNetwork's weights are on {nd}, the agent on {dev}")
+
+    @torch.no_grad()
+    def ntuple_actions(self, boards: torch.Tensor, policy) -> tuple[torch.Tensor, torch.Tensor]:
+        """The NTuplePolicy's choice on arbitrary boards (g2048_ntuple_choose / g2048_sized_ntuple_choose), the
+        analogue of search_actions: boards int64, [...] bitboards at 4 x 4 or [W, ...] planes otherwise.  Returns
+        (actions uint8 [...], q int64 [..., 4]): q[..., a] = Q_depth(board, a), -2^63 for an invalid action; a board
+        with no valid action gets action 0."""
+        from .ntuple import NTuplePolicy
+
+        if not isinstance(policy, NTuplePolicy):
+            raise TypeError(f"ntuple_actions labels boards with an NTuplePolicy (got {type(policy).__name__})")
+        self._check_network(policy.network)
+        flat, shape, head = policy.network._flat_boards(boards)
+        self._check_network_device(policy.network)
+        m = flat.shape[-1]
+        actions = torch.empty(m, dtype=torch.uint8, device=self.device)
+        q = torch.empty(m, 4, dtype=torch.int64, device=self.device)
+        d = policy._ntuple()
+        name = "g2048_sized_ntuple_choose" if self._sized else "g2048_ntuple_choose"
+        L.check(getattr(self._lib, name)(*head, ctypes.byref(d), L.ptr(flat), m, L.ptr(actions), L.ptr(q), self._stream))
+        self._paths["ntuple_actions"] = name + " (one board per thread)"
+        return actions.view(shape), q.view(shape + (4,))
+
+    @torch.no_grad()
+    def ntuple_update(self, batch: TrajectoryBatch, network, lr_num: int, lr_shift: int) -> dict:
+        """One afterstate TD(0) update of `network`'s weights, in place, from every row of `batch` (g2048_ntuple_td_update
+        / g2048_sized_ntuple_td_update; include/g2048_ntuple.h states the arithmetic): step = clamp(floor(delta lr_num /
+        2^lr_shift), -2^30, 2^30) added to the 8 B entries of the row's afterstate, with every V taken on the weights as
+        they were before the call.  lr_num in 1..65536, lr_shift in 0..40.  Returns {"rows": rows updated, "abs_delta":
+        the sum of |delta| (value units times 2^10), "path": what ran}; last_paths()["ntuple_update"] names it too.
+        All integers, and integer adds commute: the weights after the call do not depend on the order in which rows
+        are processed, and per-rank step sums could later be all-reduced exactly (data parallelism over ranks is not
+        implemented here)."""
+        self._check_network(network)
+        for name, v, lo, hi in (("lr_num", lr_num, 1, L.NTUPLE_MAX_LR_NUM), ("lr_shift", lr_shift, 0, L.NTUPLE_MAX_LR_SHIFT)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= v <= hi:
+                raise ValueError(f"{name} must be an integer in {lo}..{hi}, got {v!r}")
+        if not isinstance(batch, TrajectoryBatch):
+            raise TypeError(f"ntuple_update trains on a TrajectoryBatch (got {type(batch).__name__})")
+        self._check_network_device(network)
+        n, T = batch.n, batch.T
+        name = "g2048_sized_ntuple_td_update" if self._sized else "g2048_ntuple_td_update"
+        path = name + " (two passes: row values, then int32 atomic adds)"
+        # the batch is this agent's: board layout ([T, n] bitboards, or [W, T, n] planes), row shapes and device
+        boards = batch.boards
+        W = (self.size * self.size + 15) // 16
+        want = (W, T, n) if self._sized else (T, n)
+        if boards.dtype != torch.int64 or tuple(boards.shape) != want:
+            raise ValueError(f"batch.boards must be int64 of shape {want} for board size {self.size} (got "
+                             f"{boards.dtype}, {tuple(boards.shape)})")
+        if tuple(batch.flags.shape) != (T, n) or batch.lengths.dtype != torch.int32:
+            raise ValueError("batch.flags must be [T, n] and batch.lengths int32 [n]")
+        for t in (boards, batch.actions, batch.flags, batch.lengths):
+            if t.device.type != self.device.type:
+                raise ValueError(f"the batch is on {t.device}, the agent on {self.device}")
+        self._paths["ntuple_update"] = path
+        if n == 0 or T == 0:
+            return {"rows": 0, "abs_delta": 0, "path": path}
+        # rows sliced out of a larger capacity keep their plane stride: no copy (the sized call takes board_stride)
+        stride = T * n
+        if self._sized and boards.stride(2) == 1 and boards.stride(1) == n and boards.stride(0) >= T * n:
+            stride = boards.stride(0)
+        else:
+            boards = boards.contiguous()
+        actions, flags, lengths = batch.actions.contiguous(), batch.flags.contiguous(), batch.lengths.contiguous()
+        scratch = torch.empty(2 * T * n, dtype=torch.int64, device=self.device)
+        stats = torch.empty(2, dtype=torch.int64, device=self.device)
+        d = network._descriptor()
+        head = (self.size, ctypes.byref(d), boards.data_ptr(), stride) if self._sized else (ctypes.byref(d), L.ptr(boards))
+        L.check(getattr(self._lib, name)(*head, L.ptr(actions), L.ptr(flags), L.ptr(lengths), n, T, int(lr_num),
+                                         int(lr_shift), L.ptr(scratch), L.ptr(stats), self._stream))
+        network.weights_changed()
+        rows, abs_delta = (int(v) for v in stats.tolist())
+        return {"rows": rows, "abs_delta": abs_delta, "path": path}
+
     def trajectories_from_batch(self, batch: TrajectoryBatch, with_states: bool = True) -> list[dict[str, Any]]:
         """Convert a device batch to the reference's trajectory dicts (src/reinforce_agent.py:240-247)."""
         n, T = batch.n, batch.T
@@ -1774,10 +1892,11 @@ class ReinforceAgent:
         None mask and select_action falls back to the net, as the reference does."""
         if action_gen is None:
             return self.trajectories_from_batch(self.rollout_batch([env_seed], [policy_seed], use_greedy))[0]
+        from .ntuple import NTuplePolicy
         from .policies import ExpectimaxPolicy, PriorityPolicy, UniformPolicy
 
-        if isinstance(action_gen, (UniformPolicy, ExpectimaxPolicy)) or (isinstance(action_gen, PriorityPolicy) and
-                                                                         self.env_config.use_action_mask):
+        if isinstance(action_gen, (UniformPolicy, ExpectimaxPolicy, NTuplePolicy)) or (
+                isinstance(action_gen, PriorityPolicy) and self.env_config.use_action_mask):
             return self.trajectories_from_batch(
                 self.rollout_batch([env_seed], [policy_seed], action_gen=action_gen))[0]
         from .env import Game2048Env

@@ -306,7 +306,7 @@ def evaluation_loop(agent: ReinforceAgent, eval_cfg: Dict[str, Any], chunk: int 
     """runner.py:737-828: num_episodes episodes with fixed seed streams (greedy by default), batched.
     score_only: play them through agent.evaluate_batch (no trajectory rows: memory does not depend on the episodes'
     lengths) instead of rollout_batch; the same episodes and the same summary.
-    action_gen: a PriorityPolicy / UniformPolicy / ExpectimaxPolicy plays the episodes instead of the agent's net (the
+    action_gen: a PriorityPolicy / UniformPolicy / ExpectimaxPolicy / NTuplePolicy plays the episodes instead of the agent's net (the
     baselines a trained net is judged against); passed through to rollout_batch / evaluate_batch."""
     n = int(eval_cfg["num_episodes"])
     greedy = bool(eval_cfg.get("use_greedy", True))
