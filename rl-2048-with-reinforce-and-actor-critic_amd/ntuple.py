@@ -70,12 +70,13 @@ def dihedral_images(cells, n: int) -> list:
 
 
 def _slide_score(line):
-    """One line moved towards its first cell (exponents, 0 = empty): (new line, sum of the merged tiles' values)."""
+    """One line moved towards its first cell (exponents, 0 = empty): (new line, sum of the merged tiles' values).  As
+    on the device's nibble board, a 2^15 + 2^15 merge leaves 2^15 on the board; its gain is the true 65536."""
     tiles = [e for e in line if e]
     out, score, i = [], 0, 0
     while i < len(tiles):
         if i + 1 < len(tiles) and tiles[i] == tiles[i + 1]:
-            out.append(tiles[i] + 1)
+            out.append(min(tiles[i] + 1, 15))
             score += 1 << (tiles[i] + 1)
             i += 2
         else:

@@ -136,9 +136,11 @@ int td(const nt::Net& net, int32_t* w, const uint64_t* boards, const uint8_t* ac
     const int64_t rows = n * T;
     std::vector<int64_t> v(rows, 0), q(rows, 0);
     std::vector<uint64_t> ms(rows * G::kWords, 0);
+    std::vector<int64_t> len(n, 0);      // lengths clamped to 0..T, as pass 2 of the kernels clamps them
+    for (int64_t i = 0; i < n; i++) len[i] = lengths[i] < 0 ? 0 : lengths[i] > T ? T : lengths[i];
     for (int64_t r = 0; r < rows; r++) {
         const int64_t t = r / n, i = r % n;
-        if (t >= lengths[i]) continue;
+        if (t >= len[i]) continue;
         uint64_t b[G::kWords], m[G::kWords];
         for (int k = 0; k < G::kWords; k++) b[k] = boards[k * rows + r];
         nt::td_row_values<G>(b, actions[r], net, m, v[r], q[r]);
@@ -147,9 +149,9 @@ int td(const nt::Net& net, int32_t* w, const uint64_t* boards, const uint8_t* ac
     stats[0] = stats[1] = 0;
     for (int64_t r = 0; r < rows; r++) {
         const int64_t t = r / n, i = r % n;
-        if (t >= lengths[i]) continue;
+        if (t >= len[i]) continue;
         int64_t y;
-        if (!nt::td_target((uint32_t)t, (uint32_t)lengths[i], flags[r], t + 1 < lengths[i] ? q[r + n] : 0, y)) continue;
+        if (!nt::td_target((uint32_t)t, (uint32_t)len[i], flags[r], t + 1 < len[i] ? q[r + n] : 0, y)) continue;
         const int64_t d = y - v[r];
         stats[0] += 1;
         stats[1] += d < 0 ? -d : d;
