@@ -70,10 +70,35 @@ __device__ uint64_t g_diag_ts[kDiagBlocks * kDiagSlots];
         if (threadIdx.x == 0 && blockIdx.x < kDiagBlocks)                                       \
             g_diag_ts[blockIdx.x * kDiagSlots + (slot)] = __builtin_amdgcn_s_memrealtime();     \
     } while (0)
+// per-wave stamps of the last step launch (every wave of every workgroup; lane 0 writes them): the time the wave's
+// last sweep ended -- before its resets are appended and before the barrier -- and the number of sweeps it ran
+constexpr int kDiagWaves = kDiagBlocks * 16;
+__device__ uint64_t g_diag_wave[kDiagWaves * 2];
+#define G2048_WAVE_SWEPT() (++diag_sweeps)
+#define G2048_WAVE_DONE()                                                           \
+    do {                                                                            \
+        if ((threadIdx.x & 63) == 0 && blockIdx.x < kDiagBlocks) {                  \
+            const uint32_t w_ = blockIdx.x * 16 + (threadIdx.x >> 6);               \
+            g_diag_wave[2 * w_] = __builtin_amdgcn_s_memrealtime();                 \
+            g_diag_wave[2 * w_ + 1] = diag_sweeps;                                  \
+        }                                                                           \
+    } while (0)
 #else
 #define G2048_TS(slot) \
     do {               \
     } while (0)
+#define G2048_WAVE_SWEPT() \
+    do {                   \
+    } while (0)
+#define G2048_WAVE_DONE() \
+    do {                  \
+    } while (0)
+#endif
+
+// G2048_STEP_CLAIM=0 (tools/build_variants.py; never the shipped library): the static chunk map on the three-cell
+// path too -- the form the LDS chunk tickets were measured against (DESIGN.md "LDS chunk tickets").
+#ifndef G2048_STEP_CLAIM
+#define G2048_STEP_CLAIM 1
 #endif
 
 constexpr int kBlock = 1024;                  // 16 waves per CU; one workgroup per CU (registers: 4 waves per SIMD)
@@ -412,7 +437,10 @@ __device__ inline uint64_t step_lane(const StepArgs& a, uint32_t i, LaneIn& x, c
     const bool done = bits_done(bits);
     const bool invalid = !changed && !done;
     const double r = env_reward_nz<RK == 1>(a.rc, s, nzm, done, invalid, mt);
-    const bool trunc = a.max_steps >= 0 && (int64_t)sc >= a.max_steps && !done;
+    // max_steps as one 32-bit bound (None, or a bound the 20-bit count cannot reach: never): the 64-bit form costs the
+    // loop an SGPR pair for the value and another for its sign test
+    const uint32_t trunc_at = (uint64_t)a.max_steps > (uint64_t)G2048_LS_STEP_MASK ? ~0u : (uint32_t)a.max_steps;
+    const bool trunc = sc >= trunc_at && !done;
     const uint32_t fl = (changed ? G2048_F_CHANGED : 0u) | (done ? G2048_F_TERMINATED : 0u) |
                         (trunc ? G2048_F_TRUNCATED : 0u) | (invalid ? G2048_F_INVALID : 0u) |
                         (s.overflow ? G2048_F_OVERFLOW : 0u);
@@ -420,7 +448,10 @@ __device__ inline uint64_t step_lane(const StepArgs& a, uint32_t i, LaneIn& x, c
     if (EXTRA && a.out.reward64) st(a.out.reward64, i, r);
     if (LIST && a.out.merged) st(a.out.merged, i, s.list);
     if (EXTRA && a.out.score_add) st(a.out.score_add, i, s.score);
-    reset = (done || trunc) && a.auto_reset;   // board / lane state / obs are rewritten by reset_lane after the loop
+    // board / lane state / obs are rewritten by reset_lane after the loop.  (auto_reset enters as the flag bit it sets, a
+    // 32-bit select operand, and not as a condition of its own, which the loop would keep as a 64-bit lane mask.)
+    const uint32_t reset_bit = (done || trunc) ? (a.auto_reset ? (uint32_t)G2048_F_RESET : 0u) : 0u;
+    reset = reset_bit != 0u;
     // A resetting lane stores this step's board / state / stream / mask / obs like any other lane (reset_lane
     // overwrites them after the loop): the sweep's stores then cover whole lines.  A hole left for the reset pass
     // is written back as a partial line, and filled later by another partial write; HBM3E has no byte mask, so
@@ -428,7 +459,7 @@ __device__ inline uint64_t step_lane(const StepArgs& a, uint32_t i, LaneIn& x, c
     // synthetic start, 2-3 % of lanes resetting, ran 34 us against 29 us later; tools/step_launch_probe.py).
     uint32_t nst = sc | (mt << G2048_LS_MAXT_SHIFT) | ((done || trunc) ? 0u : G2048_LS_ACTIVE);
     if constexpr (RNG == G2048_RNG_PCG64) nst |= x.g.has_uint32 ? G2048_LS_HAS_U32 : 0u;
-    st(a.out.flags, i, (uint8_t)(fl | (reset ? G2048_F_RESET : 0u)));
+    st(a.out.flags, i, (uint8_t)(fl | reset_bit));
     st(L.board, i, m);
     st(L.state, i, nst);
     if constexpr (RNG == G2048_RNG_PCG64) store_pcg(L, i, x.g, false);
@@ -438,23 +469,17 @@ __device__ inline uint64_t step_lane(const StepArgs& a, uint32_t i, LaneIn& x, c
 }
 
 // One sweep of one wave: the step of board w0 + lane (inputs already in registers), its mask, the wave's obs.
-// A lane's first pending reset has its seed read here (`pseed`), so the read is long complete at the tail.
-template <int OBS, int RNG, int XO, int RK>
+// `note_reset(reset, i, x)` records the lane's pending auto-reset (below: the static schedule's bitmask over sweeps,
+// the ticket schedule's one slot per lane); the previous seed is read there, so the read is long complete at the tail.
+template <int OBS, int RNG, int XO, int RK, class NoteReset>
 __device__ __forceinline__ void sweep(const StepArgs& a, uint32_t w0, int lane, LaneIn& x, const LineFn& lut,
-                                      const CodeFn& code, const Line3Fn& tab3, uint64_t& pending, uint64_t& pseed,
-                                      uint32_t k) {
+                                      const CodeFn& code, const Line3Fn& tab3, const NoteReset& note_reset) {
     const uint32_t i = w0 + lane;
     bool wobs = false, reset = false;
     uint32_t mbits = 0;
     uint64_t b = 0;
     if (i < a.n) b = step_lane<RNG, XO, RK>(a, i, x, lut, code, tab3, wobs, reset, mbits);
-    if (reset) {
-        if (!pending) {
-            if constexpr (RNG == G2048_RNG_PCG64) pseed = ld(a.L.seed, i);
-            else pseed = x.seed;
-        }
-        pending |= 1ull << k;
-    }
+    note_reset(reset, i, x);
     if constexpr (XO == 3) {
         if (wobs) st(a.out.mask_bits, i, (uint8_t)mbits);
     } else {
@@ -482,8 +507,32 @@ constexpr int kList3Off = kTab3Bytes;                                 // counter
 constexpr int kStep3LdsVec = (kTab3Bytes + 16 + kReset3Cap * 12) / 16;
 static_assert(kTab3Vec == kBlock, "table fill: one uint4 per thread");
 
-// The deferred auto-resets of one wave, compacted into the workgroup's LDS list (counter, lane indices, previous
-// seeds; `cap` entries).  A lane whose entry does not fit does its own reset (mass reset).
+// One round of appends to the workgroup's LDS reset list (counter, lane indices, previous seeds; `cap` entries): the
+// lanes with `has` append (i, sd).  Call it wave-uniformly, with at least one such lane.
+// OWN: a lane whose entry does not fit does its own reset; else the entry is dropped, and the caller finds such lanes
+// again (the counter still counts them: it ends above `cap`).
+template <int OBS, int RNG, bool OWN = true>
+__device__ __forceinline__ void append_round(const StepArgs& a, bool has, uint32_t i, uint64_t sd, int lane,
+                                             uint32_t* cnt, uint32_t* ridx, uint64_t* rseed, uint32_t cap) {
+    const uint64_t bal = __ballot(has);
+    const int leader = __builtin_ctzll(bal);
+    uint32_t base = 0;
+    if (lane == leader) base = atomicAdd(cnt, (uint32_t)__popcll(bal));
+    base = (uint32_t)__shfl((int)base, leader, 64);
+    const uint32_t slot =
+        base + __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
+    if (has) {
+        if (slot < cap) {
+            ridx[slot] = i;
+            rseed[slot] = sd;
+        } else if constexpr (OWN) {
+            reset_lane<OBS, RNG>(a, i, sd);   // list full (mass reset): the lane does its own
+        }
+    }
+}
+
+// The deferred auto-resets of one wave of the static schedule, compacted into the list.  A lane whose entry does not
+// fit does its own reset (mass reset).
 template <int OBS, int RNG>
 __device__ __forceinline__ void append_resets(const StepArgs& a, uint64_t pending, uint64_t pseed, uint32_t w_first,
                                               uint32_t wstride, int lane, uint32_t* cnt, uint32_t* ridx,
@@ -494,22 +543,8 @@ __device__ __forceinline__ void append_resets(const StepArgs& a, uint64_t pendin
         const uint32_t kk = has ? (uint32_t)__builtin_ctzll(pending) : 0u;
         const uint32_t i = w_first + kk * wstride + lane;
         const uint64_t sd = first ? pseed : (has ? ld(a.L.seed, i) : 0ull);
-        const uint64_t bal = __ballot(has);
-        const int leader = __builtin_ctzll(bal);
-        uint32_t base = 0;
-        if (lane == leader) base = atomicAdd(cnt, (uint32_t)__popcll(bal));
-        base = (uint32_t)__shfl((int)base, leader, 64);
-        const uint32_t slot =
-            base + __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
-        if (has) {
-            if (slot < cap) {
-                ridx[slot] = i;
-                rseed[slot] = sd;
-            } else {
-                reset_lane<OBS, RNG>(a, i, sd);   // list full (mass reset): the lane does its own
-            }
-            pending &= pending - 1ull;
-        }
+        append_round<OBS, RNG>(a, has, i, sd, lane, cnt, ridx, rseed, cap);
+        if (has) pending &= pending - 1ull;
         first = false;
     }
 }
@@ -536,8 +571,19 @@ __device__ __forceinline__ void append_resets(const StepArgs& a, uint64_t pendin
 // table, list and barriers (29.9-31.0 us against 28.8-30.2 in the same rounds: the short workgroups' loops run
 // 13.7 us at the median against 9.5); the table's load issued before the first sweeps' loads, so that the fill waits
 // for it alone (29.5-29.9 against 29.7-29.8: no difference).
-// (A dynamic schedule -- chunks claimed with device-scope atomics -- measured slower on MI355X: under this
-// kernel's streaming load an atomic's return takes microseconds, and same-address atomics serialize.)
+// Its schedule (G2048_STEP_CLAIM): the workgroup owns the chunks it owned under the static map, but only the first
+// two rounds are dealt to its waves (their loads go out before the fill); from its third sweep on a wave draws a
+// ticket from a counter beside the list's (one lane's ds_add_rtn_u32, zeroed with the list counter), and ticket t is
+// chunk t & 15 of round t >> 4 (g2048_core.h claim_lane_base).  The claim stands where the static loop forms
+// w + wstride, two sweeps ahead of the chunk's computation, so the LDS round trip sits before a prefetch.  A wave's
+// sweeps are then no arithmetic sequence, and their number has no bound: a lane keeps one pending reset (lane index,
+// previous seed) in registers, moves it to the list when it flags another, and appends the last after the loop; an
+// entry the list cannot hold is dropped, the counter still counts it, and after the dense pass the workgroup looks
+// its chunks over for lanes whose flags ask for a reset and whose state word is still the finished episode's.
+// (A dynamic schedule across workgroups -- chunks claimed with device-scope atomics -- measured slower on MI355X:
+// under this kernel's streaming load an atomic's return takes microseconds, and same-address atomics serialize.
+// The tickets stay inside one workgroup's LDS.  DESIGN.md "LDS chunk tickets" has the per-wave stamps behind them
+// and the A/B rounds.)
 // (Round 4: an XCD-aware static partition -- contiguous chunk ranges, larger for the early-dispatched XCD groups --
 // measured no gain against this strided one, profiles/round4/r4c10/ab_xcd.log.)
 template <int OBS, int RNG, bool LDS, int XO, int U, int RK>
@@ -560,7 +606,8 @@ __global__ void __launch_bounds__(kBlock) step_kernel(StepArgs a) {
     const uint32_t* tab3 = reinterpret_cast<const uint32_t*>(a.tab + kTab3Off);
     if constexpr (LDS3) {
         const uint4* src = reinterpret_cast<const uint4*>(a.tab + kTab3Off);
-        if (threadIdx.x == 0) tab_lds[kList3Off / 16] = make_uint4(0u, 0u, 0u, 0u);   // the list's counter
+        // the list's counter, and the next chunk ticket (the first two rounds are dealt statically)
+        if (threadIdx.x == 0) tab_lds[kList3Off / 16] = make_uint4(0u, 2u * kClaimWaves, 0u, 0u);
         if (!(G2048_DIAG && (a.diag & 1))) tab_lds[threadIdx.x] = src[threadIdx.x];
         __syncthreads();
         tab3 = reinterpret_cast<const uint32_t*>(tab_lds);
@@ -584,24 +631,122 @@ __global__ void __launch_bounds__(kBlock) step_kernel(StepArgs a) {
     const LineFn lut{reinterpret_cast<const uint16_t*>(tab)};
     const CodeFn code{tab + 2 * kLines};       // the merge codes (RK 0); RK 1 reads tab3 alone
     const Line3Fn t3{tab3};
+#if G2048_DIAG
+    uint32_t diag_sweeps = 0;
+#endif
+    if constexpr (LDS3 && G2048_STEP_CLAIM) {
+        // the ticket schedule: rounds 0 and 1 as dealt above, every later chunk claimed from the workgroup's counter
+        constexpr uint32_t kCap = (uint32_t)kReset3Cap;
+        uint32_t* cnt = reinterpret_cast<uint32_t*>(tab_lds + kList3Off / 16);
+        uint32_t* ridx = cnt + 4;
+        uint64_t* rseed = reinterpret_cast<uint64_t*>(ridx + kCap);
+        // The first lane of the next unclaimed chunk.  Wave-uniform, but handed on in a vector register like the
+        // static map's bases (which derive from threadIdx): as scalars the bases, with the kernel's ~40 SGPRs of
+        // pointers, spilled 12-25 SGPRs into lanes of a VGPR in the flagship.
+        const auto claim = [&]() {
+            uint32_t t = 0, tv;
+            if (lane == 0) t = atomicAdd(cnt + 1, 1u);
+            const uint32_t ts = (uint32_t)__builtin_amdgcn_readfirstlane((int)t);
+            asm volatile("v_mov_b32 %0, %1" : "=v"(tv) : "s"(ts));
+            return claim_lane_base(tv, w_first & ~(uint32_t)(kBlock - 1), wstride);
+        };
+        // one pending reset per lane (lane index, previous seed); a second one first moves the older to the list
+        constexpr uint32_t kNoSlot = ~0u;
+        uint32_t slot_i = kNoSlot;
+        uint64_t slot_seed = 0;
+        const auto note = [&](bool reset, uint32_t i, const LaneIn& x) {
+            const bool older = reset && slot_i != kNoSlot;
+            if (older) {                       // rare: every lane for itself
+                const uint32_t slot = atomicAdd(cnt, 1u);
+                if (slot < kCap) {
+                    ridx[slot] = slot_i;
+                    rseed[slot] = slot_seed;
+                }
+            }
+            if (reset) {
+                slot_i = i;
+                if constexpr (RNG == G2048_RNG_PCG64) slot_seed = ld(a.L.seed, i);
+                else slot_seed = x.seed;
+            }
+        };
+        while (w0 < wend) {                    // wave-uniform
+            const uint32_t w2 = claim();
+            load_lane<RNG>(a, lane_at(w2), C);
+            sweep<OBS, RNG, XO, RK>(a, w0, lane, A, lut, code, t3, note);
+            G2048_WAVE_SWEPT();
+            if (w1 >= wend) break;             // w2 > w1: void
+            const uint32_t w3 = claim();
+            load_lane<RNG>(a, lane_at(w3), A);
+            sweep<OBS, RNG, XO, RK>(a, w1, lane, B, lut, code, t3, note);
+            G2048_WAVE_SWEPT();
+            if (w2 >= wend) break;
+            const uint32_t w4 = claim();
+            load_lane<RNG>(a, lane_at(w4), B);
+            sweep<OBS, RNG, XO, RK>(a, w2, lane, C, lut, code, t3, note);
+            G2048_WAVE_SWEPT();
+            w0 = w3;
+            w1 = w4;
+        }
+        G2048_WAVE_DONE();
+        if (G2048_DIAG && (a.diag & 2)) slot_i = kNoSlot;
+        const bool has = slot_i != kNoSlot;
+        if (__ballot(has)) append_round<OBS, RNG, false>(a, has, slot_i, slot_seed, lane, cnt, ridx, rseed, kCap);
+        G2048_TS(2);                           // this wave's loop and append are done
+        __syncthreads();                       // the list is complete
+        G2048_TS(3);
+        const uint32_t listed = *cnt;
+        const uint32_t R = listed < kCap ? listed : kCap;
+        for (uint32_t r = threadIdx.x; r < R; r += kBlock) reset_lane<OBS, RNG>(a, ridx[r], rseed[r]);
+        if (listed > kCap) {                   // mass reset: entries were dropped (wave-uniform)
+            // The dropped lanes are those of the workgroup's chunks whose flags of this launch ask for a reset and
+            // whose state word is still the finished episode's (reset_lane stores an active one).  The barrier makes
+            // the dense pass's stores visible to the workgroup's other waves.
+            __syncthreads();
+            for (uint32_t w = w_first; w < wend; w += wstride) {
+                const uint32_t i = w + lane;
+                if (i < a.n && (ld(a.out.flags, i) & G2048_F_RESET) && !(ld(a.L.state, i) & G2048_LS_ACTIVE))
+                    reset_lane<OBS, RNG>(a, i, ld(a.L.seed, i));
+            }
+        }
+#if G2048_DIAG
+        __syncthreads();
+        G2048_TS(4);
+#endif
+        return;
+    }
     uint64_t pending = 0, pseed = 0;
     uint32_t k = 0;
+    const auto note = [&](bool reset, uint32_t i, const LaneIn& x) {
+        if (reset) {
+            if (!pending) {
+                if constexpr (RNG == G2048_RNG_PCG64) pseed = ld(a.L.seed, i);
+                else pseed = x.seed;
+            }
+            pending |= 1ull << k;
+        }
+    };
     while (w0 < wend) {                        // wave-uniform
         const uint32_t w2 = w1 + wstride;
         load_lane<RNG>(a, lane_at(w2), C);
-        sweep<OBS, RNG, XO, RK>(a, w0, lane, A, lut, code, t3, pending, pseed, k);
+        sweep<OBS, RNG, XO, RK>(a, w0, lane, A, lut, code, t3, note);
+        G2048_WAVE_SWEPT();
         if (w1 >= wend) break;
+        k++;
         const uint32_t w3 = w2 + wstride;
         load_lane<RNG>(a, lane_at(w3), A);
-        sweep<OBS, RNG, XO, RK>(a, w1, lane, B, lut, code, t3, pending, pseed, k + 1);
+        sweep<OBS, RNG, XO, RK>(a, w1, lane, B, lut, code, t3, note);
+        G2048_WAVE_SWEPT();
         if (w2 >= wend) break;
+        k++;
         const uint32_t w4 = w3 + wstride;
         load_lane<RNG>(a, lane_at(w4), B);
-        sweep<OBS, RNG, XO, RK>(a, w2, lane, C, lut, code, t3, pending, pseed, k + 2);
+        sweep<OBS, RNG, XO, RK>(a, w2, lane, C, lut, code, t3, note);
+        G2048_WAVE_SWEPT();
         w0 = w3;
         w1 = w4;
-        k += 3;
+        k++;
     }
+    G2048_WAVE_DONE();
     if (G2048_DIAG && (a.diag & 2)) pending = 0;
     if constexpr (LDS3) {
         constexpr uint32_t kCap = (uint32_t)kReset3Cap;
@@ -968,6 +1113,14 @@ int g2048_diag_times(uint64_t* out, int blocks) {
     if (blocks > kDiagBlocks) blocks = kDiagBlocks;
     G2048_HIP(hipDeviceSynchronize());
     G2048_HIP(hipMemcpyFromSymbol(out, HIP_SYMBOL(g_diag_ts), sizeof(uint64_t) * kDiagSlots * blocks, 0,
+                                  hipMemcpyDeviceToHost));
+    return blocks;
+}
+// ... and the per-wave stamps (blocks x 16 waves x {last sweep ended, sweeps run} u64)
+int g2048_diag_wave_times(uint64_t* out, int blocks) {
+    if (blocks > kDiagBlocks) blocks = kDiagBlocks;
+    G2048_HIP(hipDeviceSynchronize());
+    G2048_HIP(hipMemcpyFromSymbol(out, HIP_SYMBOL(g_diag_wave), sizeof(uint64_t) * 32 * blocks, 0,
                                   hipMemcpyDeviceToHost));
     return blocks;
 }

@@ -526,6 +526,17 @@ G2048_HD uint64_t board_move_lean3(uint64_t b, uint32_t a, const Tab3& tab3, Mov
     return g;
 }
 
+// The step kernel's chunk tickets (three-cell path): a 1024-thread workgroup owns the chunks of 64 boards at lanes
+// block_base + 64 j + r * round_lanes (block_base = 1024 * block, j < 16, round r = 0, 1, ..., round_lanes = 1024 * grid),
+// and its 16 waves draw them in this order from a counter in LDS: ticket t is chunk j = t & 15 of round t >> 4.
+// Returns the chunk's first lane; bases grow with the ticket, so the first base >= n a wave draws ends its loop and
+// every later ticket is void.  32-bit throughout: the launcher keeps n <= 2^27 and round_lanes <= max(n, 1024 * CUs),
+// and a wave draws at most three void tickets.
+constexpr uint32_t kClaimWaves = 16u;
+G2048_HD uint32_t claim_lane_base(uint32_t t, uint32_t block_base, uint32_t round_lanes) {
+    return block_base + (t & (kClaimWaves - 1u)) * 64u + (t / kClaimWaves) * round_lanes;
+}
+
 // nz / equal-neighbour masks of a board, shared by is_done and action_mask
 struct BoardBits {
     uint64_t nz, z, eqh, eqv;

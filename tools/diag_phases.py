@@ -3,7 +3,11 @@
     G2048_DIAG_LIB=tools/libg2048_diag.so python tools/diag_phases.py [--rng pcg64 --obs log2 --boards N]
 
 Prints, for a few launches after warm-up, the distribution over workgroups of: entry skew, table fill, main loop,
-reset-list build, reset pass, and the span from the first entry to the last exit (s_memrealtime, 100 MHz)."""
+reset-list build, reset pass, and the span from the first entry to the last exit (s_memrealtime, 100 MHz).  A second
+line per launch has the per-wave stamps: over workgroups, when the first, the median and the last of a workgroup's 16
+waves ended its last sweep (us after the fill), the sweeps a wave ran, and how many waves were still sweeping 1, 2
+and 4 us before the workgroup's barrier opened ([min, median, max, mean]).  The static schedule to compare with is
+the variant build `python tools/build_variants.py pdg=G2048_DIAG=1,G2048_STEP_CLAIM=0`."""
 import argparse
 import ctypes
 import json
@@ -45,6 +49,9 @@ def main():
     torch.cuda.synchronize()
     lib = L.lib()
     lib.g2048_diag_times.argtypes = [ctypes.c_void_p, ctypes.c_int]
+    waves = hasattr(lib, "g2048_diag_wave_times")      # the per-wave stamps (three-cell and static paths alike)
+    if waves:
+        lib.g2048_diag_wave_times.argtypes = [ctypes.c_void_p, ctypes.c_int]
     nb = 4096
     buf = np.zeros((nb, 5), dtype=np.uint64)
     for k in range(args.launches):
@@ -62,7 +69,30 @@ def main():
         for name, v in ph.items():
             out[name] = [round(float(np.percentile(v, q)), 2) for q in (0, 50, 100)]
         print(json.dumps(out), flush=True)
+        if waves:
+            print(json.dumps(wave_stats(lib, k, nb, buf[:got].astype(np.int64))), flush=True)
         np.save(os.path.join(ROOT, "gpurun_out", f"phases_raw_{k}.npy"), buf[:got])
+
+
+def wave_stats(lib, k, nb, t):
+    """Per-wave stamps of the last launch: when each of a workgroup's 16 waves ended its last sweep (us after the
+    workgroup's fill), and how many waves were still sweeping 1, 2 and 4 us before its barrier opened (slot 3)."""
+    wb = np.zeros((nb, 16, 2), dtype=np.uint64)
+    got = lib.g2048_diag_wave_times(wb.ctypes.data, nb)
+    w = wb[:got].astype(np.int64)
+    ok = (t[:got, 0] > 0) & (w[:, :, 0] > 0).all(axis=1)
+    t, w = t[:got][ok], w[ok]
+    done = np.sort((w[:, :, 0] - t[:, 1:2]) * 0.01, axis=1)          # us after the fill, per workgroup ascending
+    opens = (t[:, 3] - t[:, 1]) * 0.01
+    pct = lambda v: [round(float(np.percentile(v, q)), 2) for q in (0, 50, 100)]
+    out = {"launch": k, "waves": int(w.shape[0] * 16),
+           "first_wave_done": pct(done[:, 0]), "median_wave_done": pct(np.median(done, axis=1)),
+           "last_wave_done": pct(done[:, -1]), "last_minus_first": pct(done[:, -1] - done[:, 0]),
+           "barrier_opens": pct(opens), "sweeps_per_wave": pct(w[:, :, 1])}
+    for d in (1, 2, 4):
+        busy = (done > (opens[:, None] - d)).sum(axis=1)
+        out[f"waves_sweeping_{d}us_before_barrier"] = pct(busy) + [round(float(busy.mean()), 2)]
+    return out
 
 
 if __name__ == "__main__":
